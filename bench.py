@@ -16,16 +16,21 @@ One "step" = one pass of the hot path over the whole HBM-resident synthetic tabl
 Multi-GPU (--gpus N, launched by torch.distributed.run): BASELINE config 4 -- 1e10 rows in all, rank g owns rows
 [g N/world, (g+1) N/world) (--rows overrides the per-rank count), aggregates locally, exchanges GROUP partials with one
 RCCL all-to-all inside the library, merges and emits the groups it owns.  value = rows of all ranks / max-over-ranks time.
-The line of a multi-rank run also carries config 5 (the TPC-H Q1 shape over the same row ranges) in extra.cfg5_q1_shape.
+The --full line of a multi-rank run also carries config 5 (the TPC-H Q1 shape over the same row ranges) in extra.cfg5_q1_shape.
 
 Timing: one cold step (reported as extra.cold_first_step_ms), W warm-up steps, then EXACTLY K steps between barrier +
-synchronize on both sides, un-instrumented -> value / ms_per_step; then K more steps with the library's HIP-event profiler
+synchronize on both sides, un-instrumented -> value / ms_per_step; with --full, K more steps with the library's HIP-event profiler
 on -> the per-kernel durations of the `roofline` object (extra.instrumented_ms_per_step is that region's time).  At N=1 the
-line also carries cpu_baseline (the C restatement of the reference on one host core, 3e8-row sample) and, in `extra`, the
+--full line also carries cpu_baseline (the C restatement of the reference on one host core, 3e8-row sample) and, in `extra`, the
 other BASELINE configs that fit one GPU (config 3: no filter; config 2: the FilterRelation as written and fused with
 COUNT; config 5: the Q1 shape), each with a `verified_vs_oracle` object: the same query over a 1e8-row slice through the
 same product path, compared with the CPU oracle (bit for bit; config 5's uniform doubles within n * eps * sum|v|), and the
 north-star size, 1e10 rows on one GPU, as extra.rows_1e10.
+
+A plain run (no --full) does only what the headline needs: it sets up, runs the cold step and the W warm-up steps, times the
+K steps, writes the outputs of the last timed step if --dump-outputs DIR is given (DIR/k.npy and DIR/sum_v.npy, float64, sorted
+by key) and prints the line; `roofline` and `cpu_baseline` are null there.  --full adds everything else described above: the
+plan, the instrumented region and its roofline, the sum-of-sums check, the CPU baseline, the extra legs and their checks.
 
 Prints ONE compact JSON line (< 4 KB) on rank 0 as the last line of stdout: the contract's fields, `roofline`, `cpu_baseline`
 and one {frac, ms, ok} per extra leg; the full object (every leg's description and verification record) goes to
@@ -140,6 +145,18 @@ def emit_line(full, full_out=None):
     print(out, flush=True)
 
 
+def dump_outputs(result, out_dir, suffix=""):
+    """The result batch of the timed query -> out_dir/k<suffix>.npy and out_dir/sum_v<suffix>.npy, float64, sorted by key (the
+    order the groups leave the device in is unspecified; the keys are < 2^53, so float64 holds them exactly).  10^6 groups = 16 MB."""
+    import numpy as np
+    k = result.column(0).to_numpy(zero_copy_only=False)
+    s = result.column(1).to_numpy(zero_copy_only=False)
+    o = np.argsort(k, kind="stable")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"k{suffix}.npy"), k[o].astype(np.float64))
+    np.save(os.path.join(out_dir, f"sum_v{suffix}.npy"), s[o].astype(np.float64))
+
+
 def host_cpu_budget():
     """CPUs this process may actually keep busy: the cgroup's quota when there is one (a box that shows 256 cores to
     os.cpu_count() may grant a container far fewer -- and throttles EVERY thread of the container, the one that drives the GPU
@@ -205,7 +222,15 @@ def main():
                          "8-10 %% slower (0.250 ms per launch against 0.229 ms in a short run on the same box, DESIGN.md section 5) -- so the "
                          "default is the contract's: W warm-up steps, then K timed ones.  The process's very first step (pools, calibration) "
                          "is reported as extra.cold_first_step_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: plan, instrumented region and roofline, sum-of-sums check, CPU baseline, the extra legs "
+                         "and their checks against the oracle.  Without it the run times the headline query only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result of the last one as DIR/k.npy and DIR/sum_v.npy (float64, sorted by key; "
+                         "a rank's own groups as k_rank<r>.npy / sum_v_rank<r>.npy on N > 1 GPUs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -391,8 +416,10 @@ def main():
     phases_begin()
     dt, result = timed(step, args.steps, 0)
     phases_headline = phases_end(args.steps)
+    if args.dump_outputs:
+        dump_outputs(result, args.dump_outputs, "" if world == 1 else f"_rank{rank}")
     plan_text = "n/a"
-    if world == 1:  # physical plan of the timed query after one more (untimed) run: fusion, kernel family, strategy, groups
+    if world == 1 and args.full:  # physical plan of the timed query after one more (untimed) run: fusion, kernel family, strategy, groups
         try:
             plan_agg = build(pred, [Column(0)], [sum_v])
             plan_agg.next()
@@ -403,17 +430,19 @@ def main():
     total_rows = n_rows * world
     value = total_rows * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
-    sync()
-    ex.profile_reset()
-    ex.profile_enable(True)
-    dt_instr, _ = timed(step, args.steps, 0)
-    ex.profile_enable(False)
-    prof = {p["kernel"]: p for p in ex.profile_snapshot()}
+    dt_instr, prof = None, {}
+    if args.full:
+        sync()
+        ex.profile_reset()
+        ex.profile_enable(True)
+        dt_instr, _ = timed(step, args.steps, 0)
+        ex.profile_enable(False)
+        prof = {p["kernel"]: p for p in ex.profile_snapshot()}
 
     # the oracle's side of the per-configuration checks below: started now, on host threads of their own, so that they run
     # beside the remaining GPU measurements (the headline regions above are not disturbed) and are joined when needed
     verify_rows = int(min(args.verify_rows, n_rows))
-    want_extras = (not args.no_extras) and world == 1
+    want_extras = args.full and (not args.no_extras) and world == 1
     want_oracle = want_extras and rank == 0 and not args.no_cpu_baseline
     seed2 = 0xDF01
     syn_lat = [("lat", ex.SYNTH_F64_UNIFORM, 0, 49.0, 10.0)]  # lat = 49 + 10 u, seed 0xDF01
@@ -562,12 +591,14 @@ def main():
             ts, tc = float(t[0].item()), int(t[1].item())
         return bool(local_sum == ts and local_groups == GROUPS and abs(tc / rows_total_here - 0.2) < 1e-3)
 
-    verified = sum_of_sums_check(table, result, total_rows)
-
-    extra = {"plan": plan_text.strip().split("\n"),
-             "kernels": {k: {"launches": v["launches"], "total_ms": round(v["total_ms"], 3)} for k, v in prof.items()},
-             "verified_sum_of_group_sums_equals_ungrouped_sum": verified, "device": info["name"],
-             "groups": GROUPS, "selectivity": 0.2, "instrumented_ms_per_step": dt_instr / args.steps * 1e3}
+    if args.full:
+        verified = sum_of_sums_check(table, result, total_rows)
+        extra = {"plan": plan_text.strip().split("\n"),
+                 "kernels": {k: {"launches": v["launches"], "total_ms": round(v["total_ms"], 3)} for k, v in prof.items()},
+                 "verified_sum_of_group_sums_equals_ungrouped_sum": verified, "device": info["name"],
+                 "groups": GROUPS, "selectivity": 0.2, "instrumented_ms_per_step": dt_instr / args.steps * 1e3}
+    else:
+        extra = {"device": info["name"], "groups": GROUPS, "selectivity": 0.2}
 
     def csv_leg(megabytes=1024, batch_rows=1 << 22):
         import tempfile
@@ -948,7 +979,7 @@ def main():
     # ---- config 4 AS WRITTEN on N GPUs: config 3's query -- no filter, every row routed -- over the ranks' row ranges -----
     # (the headline above keeps its 20 %-selective predicate at every N, so that the N = 1, 2, 4, 8 values are one curve; the
     # unfiltered query is 2.3 x slower per row on one GPU, and BASELINE.json's config 4 names it)
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         k4 = max(2, args.steps // 2)
         step(None)
         phases_begin()
@@ -966,7 +997,7 @@ def main():
         extra["cfg4_as_written"] = e4
 
     # ---- config 5 (TPC-H Q1 shape): one GPU as an extra, N GPUs over the ranks' row ranges -----------------
-    if (want_extras or world > 1) and not args.no_extras:
+    if (want_extras or world > 1) and args.full and not args.no_extras:
         k3 = max(2, args.steps // 2)
         n5 = n_rows if world == 1 else int(min(n_rows, 2500000000))  # 56 B/row: at most 140 GB per rank
         if world > 1:
@@ -1127,7 +1158,7 @@ def main():
 
     cpu_baseline = None
     verified_vs_oracle = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle
         for b in bg.values():  # the timed baseline below runs alone on the host
             b.t.join()

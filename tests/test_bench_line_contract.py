@@ -2,9 +2,12 @@
 profiles/r06_bench_full.json (bench.py --full-out; the line itself is its compact form, profiles/r06_bench_line.json), carries every field of the contract with consistent values -- metric / unit of BASELINE.json,
 whole-job value = rows / time, the roofline object of the dominant kernel (frac = achieved / peak, algorithmic bytes, PMC
 traffic), the CPU baseline of the oracle port -- and every extra leg that claims a roofline also says whether it was checked
-against the oracle.  CPU only: it guards the shape of what bench.py prints, not the numbers."""
+against the oracle.  The CPU tests guard the shape of what bench.py prints, not the numbers; the one GPU test runs a plain
+bench.py over a small table and checks its line and the outputs it dumps."""
 import json
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -131,3 +134,51 @@ def test_the_committed_compact_line_is_what_the_driver_gets():
     assert d["extra"]["scaling_anchor_rows_per_s"] == round(full["extra"]["rows_1e10"]["rows_per_s"], 3)
     assert all(leg.get("ok", True) is True for leg in d["extra"]["legs"].values())
     assert full["extra"]["csv_ingest_1gb"]["verified_vs_oracle"]["every_record"]["columns_bit_exact"] is True
+
+
+def test_dump_outputs_writes_the_result_sorted_by_key_as_float64(tmp_path):
+    """bench.py --dump-outputs DIR: the result batch of the last timed step -> DIR/k.npy, DIR/sum_v.npy (float64, key order)."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import pyarrow as pa
+    import bench
+    k = np.array([7, 3, 999999, 0, 42], dtype=np.int64)
+    s = np.array([1.5, -2.25, 3.0, 0.0, 2.0 ** -10], dtype=np.float64)
+    bench.dump_outputs(pa.RecordBatch.from_arrays([pa.array(k), pa.array(s)], names=["k", "SUM(v)"]), str(tmp_path / "out"))
+    gk, gs = np.load(tmp_path / "out" / "k.npy"), np.load(tmp_path / "out" / "sum_v.npy")
+    assert gk.dtype == np.float64 and gs.dtype == np.float64
+    o = np.argsort(k)
+    assert np.array_equal(gk, k[o].astype(np.float64)) and np.array_equal(gs.view(np.uint64), s[o].view(np.uint64))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_line_and_dumps_what_it_computed(tmp_path):
+    """A plain run (no --full) over a small table: the line carries the contract's fields for exactly --steps timed steps, and the
+    dumped result of the last step is the CPU oracle's, group for group and bit for bit (exact data)."""
+    import subprocess
+    import sys
+    import numpy as np
+    import oracle
+    from datafusion_archive_amd import execution as ex
+    from datafusion_archive_amd.logicalplan import AggregateFunction, BinaryExpr, Column, DataType, Literal, Operator, ScalarValue
+    rows, steps = 20000000, 3
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--rows", str(rows),
+                        "--dump-outputs", str(out), "--full-out", str(tmp_path / "full.json")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "rows/sec filter+GROUP-BY-SUM over Float64 Arrow" and d["unit"] == "rows/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == steps and d["config"]["rows_per_gpu"] == rows
+    assert abs(d["value"] - rows / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None  # the extras are --full's
+    gk, gs = np.load(out / "k.npy"), np.load(out / "sum_v.npy")
+    assert gk.dtype == np.float64 and gs.dtype == np.float64
+    syn = [("k", ex.SYNTH_I64_UNIFORM, 0, 1e6, 0.0), ("v", ex.SYNTH_F64_EXACT, 1, 0.0, 0.0)]  # bench.py's table
+    v = BinaryExpr(Column(1), Operator.Gt, Literal(ScalarValue.Float64(204.8)))
+    pred = BinaryExpr(v, Operator.And, BinaryExpr(Column(1), Operator.Lt, Literal(ScalarValue.Float64(409.6))))
+    _secs, _kept, want = oracle.run_synth_query(syn, 0xDF02, 0, rows, 1024, pred, [Column(0)],
+                                                [AggregateFunction("SUM", [Column(1)], DataType.Float64)])
+    wk, ws = want.column(0).to_numpy(), want.column(1).to_numpy()
+    o = np.argsort(wk, kind="stable")
+    assert np.array_equal(gk, wk[o].astype(np.float64)) and np.array_equal(gs.view(np.uint64), ws[o].view(np.uint64))

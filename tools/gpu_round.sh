@@ -52,7 +52,7 @@ suite)
   timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "gpu suite rc=$?"; tail -n 8 $OUT/pytest_gpu.log | cut -c1-300
   ;;
 bench)
-  SECONDS=0; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full-out $OUT/bench_full.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench took $SECONDS s"; echo "bench rc=$?  last stdout line: $(tail -n 1 $OUT/bench.json | wc -c) bytes"; tail -n 3 $OUT/bench.err | cut -c1-300
+  SECONDS=0; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --full-out $OUT/bench_full.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench took $SECONDS s"; echo "bench rc=$?  last stdout line: $(tail -n 1 $OUT/bench.json | wc -c) bytes"; tail -n 3 $OUT/bench.err | cut -c1-300
   python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -68,7 +68,7 @@ PY
   ;;
 profile)
   cd /tmp
-  BENCH="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full-out $OUT/bench_under_rocprof_full.json"
+  BENCH="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --full-out $OUT/bench_under_rocprof_full.json"
   rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o out -- $BENCH > $OUT/bench_under_rocprof.json 2>/dev/null
   cp $OUT/stats/out_kernel_stats.csv $OUT/bench_kernel_stats.csv 2>/dev/null
   export DFX_NO_TORCH=1
@@ -150,7 +150,7 @@ PY
   ;;
 dry8)
   export DFX_BENCH_SHARED_GPU=1 DFX_RCCL_LIB=$R/tests/native/librccl_stub.so
-  timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --rows 5e7 --steps 2 --warmup 1 --full-out $OUT/bench_8rank_full.json > $OUT/bench_8rank.json 2> $OUT/bench_8rank.err; echo "8-rank dry run rc=$?"; tail -2 $OUT/bench_8rank.err | cut -c1-300
+  timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --rows 5e7 --steps 2 --warmup 1 --full --full-out $OUT/bench_8rank_full.json > $OUT/bench_8rank.json 2> $OUT/bench_8rank.err; echo "8-rank dry run rc=$?"; tail -2 $OUT/bench_8rank.err | cut -c1-300
   python - $OUT/bench_8rank_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
