@@ -2666,10 +2666,24 @@ int32_t dfx_aggregate_relation_new_with_options(const struct ArrowSchema* schema
     std::vector<dfx_runtime_expr> g, a;
     for (int i = 0; i < n_group; ++i) g.push_back(*group_exprs[i]);
     for (int i = 0; i < n_aggr; ++i) a.push_back(*aggr_exprs[i]);
-    std::unique_ptr<Relation> rel(new AggregateRelation(si, std::move(in), std::move(g), std::move(a), std::move(ov)));
+    std::unique_ptr<Relation> rel;
+    if (has_distinct_aggregate(a)) {  // COUNT(DISTINCT): its own relation around a plain aggregate (dfx_distinct.cpp)
+      st = make_distinct_aggregate(si, std::move(in), std::move(g), std::move(a), std::move(ov), &rel);
+      if (!st.ok()) return to_c(st, err, errlen);
+      export_relation(std::move(rel), out);
+      return DFX_OK;
+    }
+    rel.reset(new AggregateRelation(si, std::move(in), std::move(g), std::move(a), std::move(ov)));
     export_relation(std::move(rel), out);
     return DFX_OK;
   });
+}
+
+static const char kDistinctExchange[] =
+    "COUNT_DISTINCT: distinct counts do not add across ranks (the exchange of (key, value) tuples is not implemented)";
+static bool is_distinct_stream(struct ArrowArrayStream* s) {
+  Relation* r = peek_exported(s);
+  return r && r->kind() == REL_DISTINCT_AGGREGATE;
 }
 
 static AggregateRelation* as_aggregate(struct ArrowArrayStream* s) {
@@ -2681,6 +2695,7 @@ static AggregateRelation* as_aggregate(struct ArrowArrayStream* s) {
 int32_t dfx_aggregate_partial_build(struct ArrowArrayStream* agg, int32_t world, int32_t* n_words, int64_t* counts,
                                     char* err, size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
+    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     int nw = 0;
@@ -2693,6 +2708,7 @@ int32_t dfx_aggregate_partial_build(struct ArrowArrayStream* agg, int32_t world,
 int32_t dfx_aggregate_partial_export(struct ArrowArrayStream* agg, void* dst_device, int64_t dst_words, char* err,
                                      size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
+    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     return to_c(a->partial_export(dst_device, dst_words), err, errlen);
@@ -2702,6 +2718,7 @@ int32_t dfx_aggregate_partial_export(struct ArrowArrayStream* agg, void* dst_dev
 int32_t dfx_aggregate_partial_import(struct ArrowArrayStream* agg, const void* src_device, const int64_t* counts,
                                      int32_t n_buckets, char* err, size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
+    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     return to_c(a->partial_import(src_device, counts, n_buckets), err, errlen);

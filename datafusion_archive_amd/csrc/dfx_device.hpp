@@ -366,6 +366,13 @@ struct DevDict {
   uint64_t pool_cap;
 };
 
+// COUNT(DISTINCT) (dfx_k_distinct_inl.hpp): the key columns of the emitted groups, read as the fused program sees them (load_canonical: the GROUP BY's 64-bit images;
+// Utf8 keys: the distinct side's dictionary ids, UInt64)
+struct DevDistinctKeys {
+  const void* values[kMaxKeys];
+  uint8_t dtype[kMaxKeys];
+};
+
 // ---- CSV source (dfx_k_csv.hip) -------------------------------------------------------------------------
 constexpr int kCsvMaxCols = 32;
 struct DevCsvCol {

@@ -7,6 +7,9 @@
 //   D1  numeric->numeric CAST of any scalar expression is implemented (Rust `as`); the reference
 //       implements column->Int16/Int32 and literal Int64->Float64 only (expression.rs:272-280,
 //       :345-368), `unimplemented!()` / NotImplemented / General otherwise.
+//   D8  COUNT_DISTINCT (AggregateType::CountDistinct, expression.rs:37, has no executor in the reference): the number of
+//       distinct non-null argument values, UInt64; -0.0 and +0.0 are one value, every NaN payload is one value; never null
+//       when grouped (0 for a group of null arguments), ungrouped over nothing counted what COUNT(x) gives (dfx_distinct.cpp).
 //   D6  RuntimeExpr type of a column cast is the TARGET type; the reference reports the source
 //       column's type (expression.rs:324, a bug: the array it builds has the target type).
 #include <charconv>
@@ -736,6 +739,10 @@ int32_t dfx_compile_expr(const dfx_expr_node* nodes, int32_t n_nodes, int32_t ro
     else if (!strcasecmp(nm, "count")) f = AGG_COUNT;
     else if (!strcasecmp(nm, "sum")) f = AGG_SUM;
     else if (!strcasecmp(nm, "avg")) f = AGG_AVG;  // deviation D7: typed by the planner (sqlplanner.rs:309-322), no executor in the reference
+    // deviation D8: AggregateType::CountDistinct (expression.rs:37) has no executor in the reference either.  The number of distinct
+    // non-null argument values, UInt64, per group; -0.0 == +0.0 and one NaN; ungrouped over nothing counted, what COUNT(x) gives
+    // (dfx_distinct.cpp runs it beside a plain AggregateRelation)
+    else if (!strcasecmp(nm, "count_distinct")) f = AGG_COUNT_DISTINCT;
     if (f < 0)  // expression.rs:103-106
       return to_c(Status::Err(DFX_GENERAL, std::string("Unsupported aggregate function '") + nm + "'"), err, errlen);
     e->is_aggregate = true;

@@ -144,6 +144,10 @@ struct Counters {
   long long xchg_host_syncs = 0;     // ... and their host synchronisations (2 per query)
   long long xchg_exchange_us = 0;    // counts, buffers, payload rounds, merge kernels, the closing agreement
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
+  // COUNT(DISTINCT) (dfx_distinct.cpp)
+  long long distinct_set_growths = 0;  // distinct sets rehashed into larger ones
+  long long distinct_spill_rows = 0;   // rows replayed from a distinct set's spill list
+  long long distinct_inserted = 0;     // tuples in the distinct sets at emit
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;
@@ -203,7 +207,8 @@ struct HostStreamOptions {
   int slots = 6;     // staged: pinned slots (slots x piece_mb of pinned memory per source)
 };
 
-enum RelationKind { REL_HOST_STREAM, REL_TABLE_SCAN, REL_FILTER, REL_PROJECT, REL_AGGREGATE, REL_CSV, REL_SORT, REL_LIMIT };
+enum RelationKind { REL_HOST_STREAM, REL_TABLE_SCAN, REL_FILTER, REL_PROJECT, REL_AGGREGATE, REL_CSV, REL_SORT, REL_LIMIT,
+                    REL_DISTINCT_AGGREGATE, REL_DISTINCT_TAP };
 
 // trait Relation (src/execution/relation.rs:27-32)
 struct Relation {
@@ -265,7 +270,7 @@ void explain_line(std::string* out, int depth, const std::string& text);
 std::string explain_program(const DevProgram& P);
 
 // ---- expressions (dfx_expr.cpp) ---------------------------------------------------------------
-enum AggregateType { AGG_MIN = 0, AGG_MAX = 1, AGG_SUM = 2, AGG_COUNT = 3, AGG_AVG = 4 };
+enum AggregateType { AGG_MIN = 0, AGG_MAX = 1, AGG_SUM = 2, AGG_COUNT = 3, AGG_AVG = 4, AGG_COUNT_DISTINCT = 5 };
 
 }  // namespace dfx
 

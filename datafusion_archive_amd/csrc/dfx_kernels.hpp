@@ -30,6 +30,8 @@ enum KernelId : int {
   KID_PARTITION_AGG,
   KID_CSV,
   KID_SORT,
+  KID_DISTINCT_INSERT,
+  KID_DISTINCT_COUNT,
   KID_COUNT_
 };
 const char* kernel_name(int kid);
@@ -208,6 +210,16 @@ hipError_t launch_gather_bits(const uint8_t* const* bases, const int64_t* bit_of
 hipError_t launch_gather_utf8_lens(const int32_t* const* offsets, const uint64_t* loc, int64_t n, int32_t* lens, hipStream_t s);
 hipError_t launch_gather_utf8_copy(const int32_t* const* offsets, const uint8_t* const* data, const uint64_t* loc, int64_t n,
                                    const int32_t* dst_offsets, uint8_t* out, hipStream_t s);
+
+// COUNT(DISTINCT x) (dfx_k_distinct*.hip, deviation D8): distinct sets are DevTables with na == 0 whose key is the tuple
+// (group key words, zero padding, canonical argument image); growth and spill replay use launch_rehash / launch_merge_rows.
+// insert: rows -> tuples (null arguments skipped, floats canonicalised) -> set, rows it cannot take -> spill; *plan_kernel: the
+// scan-plan flavour ran (else the SSA interpreter).  count: ungrouped (S.kw == 1) the tuples into *total, grouped +1 per tuple
+// into the count table Cnt (key prefix, one ACC_ADD_U64).  lookup: emitted group keys -> counts (0 when absent).
+hipError_t launch_distinct_insert(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan, int kw_out,
+                                  const DevTable& T, const DevRows& spill, int64_t n, bool* plan_kernel, hipStream_t s);
+hipError_t launch_distinct_count(const DevTable& S, const DevTable& Cnt, uint64_t* total, hipStream_t s);
+hipError_t launch_distinct_lookup(const DevTable& Cnt, const DevDistinctKeys& K, int kw_out, int64_t n, uint64_t* out, hipStream_t s);
 
 // synthetic columns (definition shared with oracle/dfx_oracle.c: orc_synth_fill)
 hipError_t launch_synth(int kind, int column_id, double p0, double p1, uint64_t seed, int64_t row_begin,

@@ -116,6 +116,7 @@ struct AggOptions {
                                // columns in ONE kernel (0: k_predicate_mask -> scan -> k_compact, the column is read twice)
   int csv_wave_tiles = 1;      // CsvDataSource cells: one wave per tile of 64 records converts from an LDS copy of the tile's text (0: every
                                // lane walks its own record in global memory -- the path tiles with quotes or ragged records take anyway)
+  int distinct_capacity_log2 = 0;  // initial slots of a COUNT(DISTINCT) set (0: 2^20); tests use tiny values to force growth
   int replay_in_place = 1;     // 1: rows spilled by a table that is NOT full (region overflow of a heavy key) are replayed into the
                                // table as it is, and only what it cannot take makes it grow (0: every spill quadruples the table)
 };
@@ -276,6 +277,13 @@ class AggregateRelation : public Relation {
   SchemaInfo schema_;
   std::unique_ptr<Impl> impl_;
 };
+
+// ---- COUNT(DISTINCT) (dfx_distinct.cpp, deviation D8) -----------------------------------------------
+// An aggregate list with a COUNT_DISTINCT runs as a relation of its own (REL_DISTINCT_AGGREGATE) around a plain
+// AggregateRelation over the other aggregates.  Limits it cannot take are returned here, at creation.
+bool has_distinct_aggregate(const std::vector<dfx_runtime_expr>& aggr);
+Status make_distinct_aggregate(SchemaInfo schema, std::unique_ptr<Relation> input, std::vector<dfx_runtime_expr> group,
+                               std::vector<dfx_runtime_expr> aggr, OptionOverrides options, std::unique_ptr<Relation>* out);
 
 // shared by filter / aggregate: CTRL_ERROR bits -> the reference's error
 Status error_from_ctrl(uint32_t bits);

@@ -243,6 +243,7 @@ bool set_option_in(AggOptions& o, const char* key, int64_t value) {
   else if (!strcmp(key, "agg.replay_in_place")) o.replay_in_place = (int)value;
   else if (!strcmp(key, "agg.partition_pad")) o.partition_pad = (int)value;
   else if (!strcmp(key, "agg.dict_capacity_log2")) o.dict_capacity_log2 = (int)value;
+  else if (!strcmp(key, "agg.distinct_capacity_log2")) o.distinct_capacity_log2 = (int)value;
   else if (!strcmp(key, "agg.partition_cap_rows")) o.partition_cap_rows = (int)value;
   else if (!strcmp(key, "agg.partition_defer")) o.partition_defer = (int)value;
   else if (!strcmp(key, "agg.partition_defer_batches")) o.partition_defer_batches = (int)value;
@@ -468,6 +469,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_pair_fallbacks")) return counters().agg_pair_fallbacks;
   if (!strcmp(name, "agg_growths")) return counters().agg_growths;
   if (!strcmp(name, "agg_shared_operand_launches")) return counters().agg_shared_operand_launches;
+  if (!strcmp(name, "distinct_set_growths")) return counters().distinct_set_growths;
+  if (!strcmp(name, "distinct_spill_rows")) return counters().distinct_spill_rows;
+  if (!strcmp(name, "distinct_inserted")) return counters().distinct_inserted;
   if (!strcmp(name, "xchg_calls")) return counters().xchg_calls;
   if (!strcmp(name, "xchg_local_us")) return counters().xchg_local_us;
   if (!strcmp(name, "xchg_wait_peers_us")) return counters().xchg_wait_peers_us;

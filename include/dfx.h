@@ -188,6 +188,8 @@ int32_t dfx_synchronize(char* err, size_t errlen);
  * Validation errors map 1:1 on the reference's Err cases (unsupported literal type :306-309,
  * unsupported operator :494-497, unsupported expression :500-503, cast rules :316-379,
  * unsupported aggregate :103-106).
+ * Aggregate names (matched case-insensitively): MIN, MAX, SUM, COUNT, AVG and COUNT_DISTINCT (one argument, return type
+ * UInt64: the number of distinct non-null argument values; a Rust shim maps AggregateType::CountDistinct to this name).
  * ---------------------------------------------------------------------------------------- */
 typedef struct dfx_runtime_expr dfx_runtime_expr;
 
@@ -223,7 +225,9 @@ int32_t dfx_project_relation_new(struct ArrowArrayStream* input, const dfx_runti
 
 /* replaces AggregateRelation::new(schema, input, group_expr, aggr_expr) + impl Relation
  * (src/execution/aggregate.rs:47-61, :614-631, :703-952).  `schema` may be NULL or empty
- * (context.rs:185 passes Schema::empty()). */
+ * (context.rs:185 passes Schema::empty()).  With a COUNT_DISTINCT among the aggregates the stream is a distinct aggregate
+ * around a plain one: more than 7 GROUP BY expressions are DFX_NOT_IMPLEMENTED here, and so are the partial / exchange
+ * calls below on such a stream (distinct counts do not add across ranks). */
 int32_t dfx_aggregate_relation_new(const struct ArrowSchema* schema, struct ArrowArrayStream* input,
                                    const dfx_runtime_expr* const* group_exprs, int32_t n_group,
                                    const dfx_runtime_expr* const* aggr_exprs, int32_t n_aggr,

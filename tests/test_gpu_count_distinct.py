@@ -1,0 +1,309 @@
+"""COUNT(DISTINCT x) on the device (deviation D8).  The truth is numpy over canonicalised value images (-0.0 is +0.0, one NaN);
+plain aggregates that share a query are compared bit for bit with the same query without the distinct aggregates."""
+import ctypes
+import os
+
+import numpy as np
+import pyarrow as pa
+import pytest
+
+import oracle
+from datafusion_archive_amd import _ffi
+from datafusion_archive_amd import execution as ex
+from datafusion_archive_amd.logicalplan import AggregateFunction, BinaryExpr, Column, DataType, Literal, Operator, ScalarValue
+from gpu_util import assert_arrays_identical
+
+pytestmark = pytest.mark.gpu
+
+DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+U64 = DataType.UInt64
+I64_MIN = -(2 ** 63)
+
+
+def cd(i):
+    return AggregateFunction("COUNT_DISTINCT", [i if not isinstance(i, int) else Column(i)], U64)
+
+
+def _rel(schema, batches, group, aggs, filter_expr=None, source=None, options=None):
+    rel = source if source is not None else ex.DataSourceRelation(schema, batches)
+    if filter_expr is not None:
+        rel = ex.FilterRelation(rel, ex.compile_scalar_expr(None, filter_expr, schema), schema)
+    return ex.AggregateRelation(None, rel, [ex.compile_scalar_expr(None, g, schema) for g in group],
+                                [ex.compile_expr(None, a, schema) for a in aggs], options)
+
+
+def run(schema, batches, group, aggs, **kw):
+    rel = _rel(schema, batches, group, aggs, **kw)
+    out = rel.next()
+    assert out is not None and rel.next() is None
+    return out
+
+
+def ragged(table, rng):
+    """the table in batches of random lengths"""
+    n, out, i = table.num_rows, [], 0
+    while i < n:
+        m = int(rng.integers(1, max(2, n // 3)))
+        out.extend(table.slice(i, m).to_batches())
+        i += m
+    return out or [pa.RecordBatch.from_pydict({f.name: pa.array([], f.type) for f in table.schema}, schema=table.schema)]
+
+
+def image(arr):
+    """numpy keys of the distinct values of a pyarrow array (nulls dropped)"""
+    a = arr.drop_null() if hasattr(arr, "drop_null") else arr.filter(arr.is_valid())
+    if pa.types.is_floating(a.type):
+        f = a.to_numpy(zero_copy_only=False)
+        f = np.where(f == 0, np.zeros_like(f), f)  # -0.0 -> +0.0
+        u = f.view(np.uint64 if f.dtype == np.float64 else np.uint32).astype(np.uint64)
+        return np.where(np.isnan(f), np.uint64(1), u + np.uint64(2))  # every NaN one value
+    if pa.types.is_string(a.type):
+        return np.array(a.to_pylist(), dtype=object)
+    return a.to_numpy(zero_copy_only=False)
+
+
+def special_values(t, rng, n):
+    if t in (pa.float32(), pa.float64()):
+        np_t = np.float64 if t == pa.float64() else np.float32
+        base = (rng.integers(-300, 300, n) * 0.25).astype(np_t)
+        nan_bits = [0x7FF8000000000001, 0xFFF0000000000123, 0x7FF8000000000000] if np_t == np.float64 else [0x7FC00001, 0xFF800123, 0x7FC00000]
+        ut = np.uint64 if np_t == np.float64 else np.uint32
+        specials = np.concatenate([np.array(nan_bits, dtype=ut).view(np_t), np.array([0.0, -0.0, np.inf, -np.inf], dtype=np_t)])
+    else:
+        info = np.iinfo(t.to_pandas_dtype())
+        base = rng.integers(-300 if info.min < 0 else 0, 300, n).astype(t.to_pandas_dtype())
+        specials = np.array([info.min, info.max, 0], dtype=t.to_pandas_dtype())
+    if n:
+        pos = rng.integers(0, n, min(n, 3 * len(specials)))
+        base[pos] = np.resize(specials, len(pos))
+    valid = rng.random(n) > 0.1
+    return pa.array(base, t, mask=~valid)
+
+
+@pytest.mark.parametrize("t", [pa.int32(), pa.int64(), pa.uint64(), pa.float32(), pa.float64()], ids=str)
+def test_ungrouped_types_sizes_and_specials(t):
+    rng = np.random.default_rng(11)
+    for n in (0, 1, 4097, 200003):
+        x = special_values(t, rng, n)
+        schema = pa.schema([("x", t)])
+        table = pa.Table.from_arrays([x], schema=schema)
+        batches = ragged(table, rng)
+        got = run(schema, batches, [], [cd(0), AggregateFunction("COUNT", [Column(0)], U64)])
+        want = len(np.unique(image(x))) if n else 0
+        cnt = got.column(1)
+        if cnt.is_valid()[0].as_py() and cnt[0].as_py() > 0:
+            assert got.column(0).to_pylist() == [want], (t, n)
+        else:  # nothing counted: exactly what COUNT(x) gives, validity and value
+            assert got.column(0).is_valid().to_pylist() == cnt.is_valid().to_pylist(), (t, n)
+            assert got.column(0).to_pylist() == cnt.to_pylist(), (t, n)
+    allnull = pa.array([None] * 1000, t)
+    got = run(pa.schema([("x", t)]), [pa.RecordBatch.from_arrays([allnull], ["x"])], [], [cd(0), AggregateFunction("COUNT", [Column(0)], U64)])
+    assert got.column(0).to_pylist() == got.column(1).to_pylist()
+
+
+def grouped_truth(keys, arg):
+    """{key tuple: distinct non-null count} over every key tuple that occurs"""
+    valid = np.asarray(arg.is_valid())
+    img = np.asarray(image(arg.fill_null("" if pa.types.is_string(arg.type) else 0)))
+    out = {}
+    seen = set()
+    for i in range(len(arg)):
+        kt = tuple(int(k[i]) for k in keys)
+        out.setdefault(kt, 0)
+        if valid[i] and (kt, img[i]) not in seen:
+            seen.add((kt, img[i]))
+            out[kt] += 1
+    return out
+
+
+def as_dict(batch, kw, col):
+    keys = [batch.column(i).to_pylist() for i in range(kw)]
+    vals = batch.column(col).to_pylist()
+    return {tuple(k[i] for k in keys): vals[i] for i in range(batch.num_rows)}
+
+
+@pytest.mark.parametrize("kw", [1, 2, 5])
+@pytest.mark.parametrize("dist", ["uniform", "zipf"])
+def test_grouped(kw, dist):
+    rng = np.random.default_rng(kw * 7 + len(dist))
+    n = 60000
+    keys = []
+    for k in range(kw):
+        if dist == "zipf":
+            c = np.minimum(rng.zipf(1.3, n), 500).astype(np.int64)
+        else:
+            c = rng.integers(0, 400 if kw == 1 else 12, n).astype(np.int64)
+        keys.append(c)
+    keys[0][:50] = I64_MIN  # the sentinel-colliding key
+    v = rng.integers(0, 150, n).astype(np.int64)
+    keys[0][50:60] = 7
+    valid = rng.random(n) > 0.2
+    valid[keys[0] == 7] = False  # groups whose arguments are all null
+    arg = pa.array(v, pa.int64(), mask=~valid)
+    schema = pa.schema([(f"k{i}", pa.int64()) for i in range(kw)] + [("v", pa.int64())])
+    table = pa.Table.from_arrays([pa.array(k) for k in keys] + [arg], schema=schema)
+    got = run(schema, ragged(table, rng), [Column(i) for i in range(kw)], [cd(kw)])
+    want = grouped_truth(keys, arg)
+    g = as_dict(got, kw, kw)
+    assert g == want
+    assert g[tuple([7] + [int(k[55]) for k in keys[1:]])] == 0
+
+
+def _sorted(batch, kw):
+    idx = pa.compute.sort_indices(pa.Table.from_batches([batch]), [(batch.schema.names[i], "ascending") for i in range(kw)])
+    return pa.Table.from_batches([batch]).take(idx)
+
+
+def test_mixed_with_plain_aggregates():
+    rng = np.random.default_rng(5)
+    n = 100000
+    k = rng.integers(0, 3000, n).astype(np.int64)
+    v = rng.integers(0, 50, n).astype(np.int64)
+    w = (rng.integers(-100, 100, n) * 0.5)
+    x = rng.integers(0, 1 << 20, n) * 2.0 ** -10
+    schema = pa.schema([("k", pa.int64()), ("v", pa.int64()), ("w", pa.float64()), ("x", pa.float64())])
+    table = pa.Table.from_arrays([pa.array(k), pa.array(v), pa.array(w, mask=rng.random(n) < 0.05), pa.array(x)], schema=schema)
+    batches = ragged(table, rng)
+    plain = [AggregateFunction("SUM", [Column(1)], DataType.Int64), AggregateFunction("AVG", [Column(3)], DataType.Float64)]
+    aggs = [plain[0], cd(2), plain[1], cd(1)]
+    got = _sorted(run(schema, batches, [Column(0)], aggs), 1)
+    assert got.schema.names == ["k", "SUM", "COUNT_DISTINCT", "AVG", "COUNT_DISTINCT"]
+    base = _sorted(run(schema, batches, [Column(0)], plain), 1)
+    for gi, bi in ((0, 0), (1, 1), (3, 2)):
+        assert_arrays_identical(got.column(gi), base.column(bi), f"column {gi}")
+    want = _sorted(oracle.aggregate([Column(0)], plain, batches), 1)
+    assert got.column(1).to_pylist() == want.column(1).to_pylist()
+    tw, tv = grouped_truth([k], table.column(2).combine_chunks()), grouped_truth([k], table.column(1).combine_chunks())
+    keys = got.column(0).to_pylist()
+    assert got.column(2).to_pylist() == [tw[(kk,)] for kk in keys]
+    assert got.column(4).to_pylist() == [tv[(kk,)] for kk in keys]
+
+
+def test_computed_argument_and_filter_below():
+    rng = np.random.default_rng(9)
+    n = 50000
+    k = rng.integers(0, 100, n).astype(np.int64)
+    a = rng.integers(0, 40, n).astype(np.int64)
+    b = rng.integers(0, 40, n).astype(np.int64)
+    schema = pa.schema([("k", pa.int64()), ("a", pa.int64()), ("b", pa.int64())])
+    batches = ragged(pa.Table.from_arrays([pa.array(k), pa.array(a), pa.array(b)], schema=schema), rng)
+    got = run(schema, batches, [Column(0)], [cd(BinaryExpr(Column(1), Operator.Plus, Column(2)))])
+    assert as_dict(got, 1, 1) == grouped_truth([k], pa.array(a + b))
+    pred = BinaryExpr(Column(2), Operator.Lt, Literal(ScalarValue.Int64(10)))
+    got = run(schema, batches, [Column(0)], [cd(1)], filter_expr=pred)
+    keep = b < 10
+    assert as_dict(got, 1, 1) == grouped_truth([k[keep]], pa.array(a[keep]))
+
+
+def test_utf8_through_csv_and_host_batches():
+    schema = pa.schema([("a", pa.string()), ("b", pa.float64())])
+    src = ex.CsvDataSource(os.path.join(DATA, "aggregate_test_2.csv"), schema, 1024)
+    got = run(schema, None, [Column(0)], [cd(1), cd(0)], source=src)
+    t = oracle.read_csv(os.path.join(DATA, "aggregate_test_2.csv"), schema, 1024)
+    rows = pa.Table.from_batches(t).to_pylist()
+    want = {}
+    for r in rows:
+        want.setdefault(r["a"], set()).add(r["b"])
+    assert {r[0]: r[1] for r in zip(*[got.column(i).to_pylist() for i in range(2)])} == {a: len(s) for a, s in want.items()}
+    assert got.column(2).to_pylist() == [1] * got.num_rows
+    people = pa.schema([("id", pa.int64()), ("first_name", pa.string())])
+    got = run(people, None, [Column(1)], [cd(0)], source=ex.CsvDataSource(os.path.join(DATA, "people.csv"), people, 1024))
+    prow = pa.Table.from_batches(oracle.read_csv(os.path.join(DATA, "people.csv"), people, 1024)).to_pylist()
+    pw = {}
+    for r in prow:
+        pw.setdefault(r["first_name"], set()).add(r["id"])
+    assert dict(zip(got.column(0).to_pylist(), got.column(1).to_pylist())) == {k: len(s) for k, s in pw.items()}
+    got = run(people, None, [], [cd(1)], source=ex.CsvDataSource(os.path.join(DATA, "people.csv"), people, 1024))
+    assert got.column(0).to_pylist() == [len(pw)]
+    # host batches of random strings: a Utf8 argument and a Utf8 key
+    rng = np.random.default_rng(3)
+    n = 30000
+    words = ["".join(chr(97 + c) for c in rng.integers(0, 26, rng.integers(0, 12))) for _ in range(2000)]
+    s = [words[i] for i in rng.integers(0, len(words), n)]
+    k = rng.integers(0, 50, n).astype(np.int64)
+    valid = rng.random(n) > 0.1
+    schema = pa.schema([("k", pa.int64()), ("s", pa.string())])
+    table = pa.Table.from_arrays([pa.array(k), pa.array(s, mask=~valid)], schema=schema)
+    batches = ragged(table, rng)
+    got = run(schema, batches, [Column(0)], [cd(1)])
+    want = {}
+    for kk, ss, ok in zip(k, s, valid):
+        want.setdefault(int(kk), set())
+        if ok:
+            want[int(kk)].add(ss)
+    assert as_dict(got, 1, 1) == {(kk,): len(v) for kk, v in want.items()}
+    table = pa.Table.from_arrays([pa.array(k), pa.array(s)], schema=schema)  # (GROUP BY reads keys without a null check)
+    got = run(schema, ragged(table, rng), [Column(1)], [cd(0)])
+    ws = {}
+    for kk, ss in zip(k, s):
+        ws.setdefault(ss, set()).add(int(kk))
+    assert dict(zip(got.column(0).to_pylist(), got.column(1).to_pylist())) == {a: len(b) for a, b in ws.items()}
+
+
+def test_growth_from_a_tiny_set():
+    rng = np.random.default_rng(13)
+    n = 1 << 21
+    k = rng.integers(0, 1 << 12, n).astype(np.int64)
+    v = rng.integers(0, 1 << 9, n).astype(np.int64)
+    schema = pa.schema([("k", pa.int64()), ("v", pa.int64())])
+    batches = pa.Table.from_arrays([pa.array(k), pa.array(v)], schema=schema).to_batches(max_chunksize=1 << 18)
+    ex.counter_reset()
+    got = run(schema, batches, [Column(0)], [cd(1)], options={"agg.distinct_capacity_log2": 9})
+    assert ex.counter_get("distinct_set_growths") >= 1 and ex.counter_get("distinct_spill_rows") >= 1
+    tup = np.unique(k * (1 << 9) + v)
+    want = np.bincount(tup >> 9, minlength=1 << 12)
+    assert ex.counter_get("distinct_inserted") == len(tup)
+    got_k = np.array(got.column(0).to_pylist())
+    assert np.array_equal(np.array(got.column(1).to_pylist()), want[got_k])
+    assert len(got_k) == len(np.unique(k))
+
+
+def test_scale_resident_synthetic_table():
+    n = 1 << 26
+    syn = [("k", ex.SYNTH_I64_UNIFORM, 0, 1e5, 0.0), ("v", ex.SYNTH_I64_UNIFORM, 1, 1000.0, 0.0)]
+    t = ex.DeviceTable.synth(syn, 77, 0, n)
+    schema = pa.schema([("k", pa.int64()), ("v", pa.int64())])
+    got = run(schema, None, [Column(0)], [cd(1)], source=t.scan(1 << 24))
+    k = oracle.synth_column(oracle.SYNTH_I64_UNIFORM, 0, 1e5, 0.0, 77, 0, n)
+    v = oracle.synth_column(oracle.SYNTH_I64_UNIFORM, 1, 1000.0, 0.0, 77, 0, n)
+    assert k.min() >= 0 and k.max() < 100000 and v.min() >= 0 and v.max() < 1000
+    mark = np.zeros(100000 * 1000, dtype=bool)
+    mark[k * 1000 + v] = True
+    del k, v
+    want = mark.reshape(100000, 1000).sum(axis=1)
+    gk = np.array(got.column(0).to_pylist())
+    assert np.array_equal(np.array(got.column(1).to_pylist()), want[gk])
+    assert len(gk) == int((want > 0).sum())
+
+
+def test_order_by_the_count_then_limit():
+    rng = np.random.default_rng(21)
+    n = 80000
+    k = rng.integers(0, 500, n).astype(np.int64)
+    v = (rng.integers(0, 1000, n) % (k + 1)).astype(np.int64)
+    schema = pa.schema([("k", pa.int64()), ("v", pa.int64())])
+    batches = pa.Table.from_arrays([pa.array(k), pa.array(v)], schema=schema).to_batches(max_chunksize=20000)
+    rel = _rel(schema, batches, [Column(0)], [cd(1)])
+    out_schema = rel.schema()
+    rel = ex.SortRelation(rel, [(ex.compile_scalar_expr(None, Column(1), out_schema), False)], out_schema)
+    rel = ex.LimitRelation(rel, 10, out_schema)
+    got = pa.Table.from_batches(list(rel))
+    truth = grouped_truth([k], pa.array(v))
+    assert got.num_rows == 10
+    assert got.column(1).to_pylist() == sorted(truth.values(), reverse=True)[:10]
+    assert all(truth[(kk,)] == c for kk, c in zip(got.column(0).to_pylist(), got.column(1).to_pylist()))
+
+
+def test_exchange_is_not_implemented():
+    schema = pa.schema([("k", pa.int64()), ("v", pa.int64())])
+    b = pa.RecordBatch.from_arrays([pa.array([1, 2, 3]), pa.array([4, 5, 6])], names=["k", "v"])
+    rel = _rel(schema, [b], [Column(0)], [cd(1)])
+    with pytest.raises(ex.ExecutionError) as ei:
+        rel.partial_build(2)
+    assert ei.value.kind == "NotImplemented"
+    rel = _rel(schema, [b], [Column(0)], [cd(1)])
+    err = ctypes.create_string_buffer(1024)
+    stats = (ctypes.c_int64 * 4)()
+    code = _ffi.lib().dfx_aggregate_exchange(ctypes.byref(rel._live_stream()), None, stats, err, 1024)
+    assert code == 5 and b"COUNT_DISTINCT" in err.value
+    assert as_dict(rel.next(), 1, 1) == {(1,): 1, (2,): 1, (3,): 1}  # the stream itself still runs
