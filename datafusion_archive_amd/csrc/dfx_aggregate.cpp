@@ -51,7 +51,20 @@ struct AggregateRelation::Impl {
     bool allocated = false;
   };
   std::vector<DictKey> dicts;
-  SchemaInfo bind_schema;                  // input schema + the virtual id columns (what the program binds to)
+  SchemaInfo bind_schema;                  // input schema + the virtual id columns + the string terms' Boolean columns (what the program binds to)
+  // Utf8 string terms of the absorbed predicate (deviation D9): their bitmaps are computed per batch beside the dictionary ids
+  // and bound as virtual Boolean columns; `pred` stays as written (the real FilterRelation of a null batch compiles its own)
+  Utf8Terms pred_terms;
+  // Several chunks of accumulators scan the same batches one after the other: the terms are evaluated ONCE per batch and the bitmaps
+  // reused by every chunk.  Entries live only inside the chunk loops of consume_batch / run_held, while the batches they were
+  // computed from are held (so a batch is safely named by its offsets pointer and row count).
+  struct TermCacheEntry {
+    const void* offsets = nullptr;
+    int64_t rows = 0;
+    std::vector<DeviceColumn> cols;  // the virtual Boolean columns, in pred_terms.terms() order
+  };
+  std::vector<TermCacheEntry> term_cache;
+  bool term_cache_on = false;
   std::vector<dfx_runtime_expr> group_rw;  // GROUP BY expressions with Utf8 columns redirected to their id columns
   std::vector<int> key_out_dtype;          // result type of each key column (DFX_UTF8 for dictionary keys)
   // result aggregates -> accumulators: AVG(x) is the pair SUM(x), COUNT(x) of consecutive accumulators, divided at
@@ -339,6 +352,10 @@ Status AggregateRelation::Impl::setup(const SchemaInfo& input_schema) {
     key_out_dtype[k] = DFX_UTF8;
     dicts.push_back(std::move(d));
   }
+  if (has_pred) {
+    DFX_RETURN_IF_ERROR(pred_terms.compile(pred, input_schema, (int)bind_schema.fields.size()));
+    pred_terms.append_fields(&bind_schema);
+  }
   kw_out = (int)group.size();
   na_total = (int)aggr.size();
   if (kw_out > kMaxKeys) return Status::Err(DFX_NOT_IMPLEMENTED, strfmt("more than %d GROUP BY expressions", kMaxKeys));
@@ -449,7 +466,8 @@ Status AggregateRelation::Impl::build_chunk_programs(Chunk& ch) {
   plan.pred = kNoOperand;
   if (has_pred) {
     int dt = 0;
-    DFX_RETURN_IF_ERROR(builder->add(pred, pred.root, &plan.pred, &dt));
+    const dfx_runtime_expr& pe = pred_terms.empty() ? pred : pred_terms.rewritten();
+    DFX_RETURN_IF_ERROR(builder->add(pe, pe.root, &plan.pred, &dt));
     if (dt != DFX_BOOLEAN) return Status::Err(DFX_EXECUTION_ERROR, "Filter expression did not evaluate to boolean");
   }
   for (int k = 0; k < kw; ++k) {
@@ -650,6 +668,11 @@ uint64_t AggregateRelation::Impl::program_fingerprint() const {
   mix(P.imm, sizeof(uint64_t) * (size_t)std::max(0, std::min<int>(P.n_imm, kMaxImm)));
   mix(P.col_dtype, sizeof(P.col_dtype));
   for (int ci : builder->columns()) mix(&ci, sizeof(ci));
+  for (const Utf8TermSpec& t : pred_terms.terms()) {  // (the literals of string terms live outside the program)
+    mix(&t.src_col, sizeof(t.src_col));
+    mix(&t.op, sizeof(t.op));
+    mix(t.literal.data(), t.literal.size());
+  }
   mix(&plan.pred, 1);
   mix(plan.key, sizeof(plan.key));
   mix(plan.arg, sizeof(plan.arg));
@@ -1255,6 +1278,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
     bool nulls = false;
     for (int ci : builder->columns())
       if (ci >= 0 && ci < (int)b.columns.size() && b.columns[(size_t)ci].validity && b.columns[(size_t)ci].null_count != 0) nulls = true;
+    if (pred_terms.source_has_nulls(b)) nulls = true;  // (a string term's own column: the Filter's all-valid output decides what the aggregate sees)
     // A scan plan evaluates the fused form with exactly those rules -- a null judged by arrow's comparison rule, every
     // surviving slot valid, value(row) read regardless (DevScanPlan::count_valid) -- in one pass: no materialised filter.
     if (nulls && opt().plan != 0 && opt().fast != 0 && scan_plan_shape_ok(builder->program(), fast, kw, na, val_xform)) {
@@ -1303,15 +1327,36 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
   hipStream_t s = ctx().stream;
   DevProgram prog;
   DevColumns cols;
-  if (dicts.empty()) {
+  const bool terms_now = has_pred && !unfused_now && !pred_terms.empty();
+  if (dicts.empty() && !terms_now) {
     DFX_RETURN_IF_ERROR(builder->bind(b, &prog, &cols));
-  } else {  // append the id column of every Utf8 key
+  } else {  // append the id column of every Utf8 key and the bitmap of every string term of the absorbed predicate
     DeviceBatch ab = b;
     ab.columns.resize(bind_schema.fields.size());
     for (DictKey& d : dicts) {
       if (d.src_col >= (int)b.columns.size() || b.columns[d.src_col].dtype != DFX_UTF8)
         return Status::Err(DFX_INTERNAL_ERROR, "GROUP BY key column is not Utf8 in this batch");
       DFX_RETURN_IF_ERROR(dict_encode(d, b.columns[d.src_col], n, &ab.columns[d.virt_col]));
+    }
+    if (terms_now) {
+      const std::vector<Utf8TermSpec>& ts = pred_terms.terms();
+      const void* key = ts[0].src_col < (int)b.columns.size() ? (const void*)b.columns[(size_t)ts[0].src_col].offsets : nullptr;
+      const TermCacheEntry* hit = nullptr;
+      if (term_cache_on && key)
+        for (const TermCacheEntry& e : term_cache)
+          if (e.offsets == key && e.rows == n) hit = &e;
+      if (hit) {
+        for (size_t k = 0; k < ts.size(); ++k) ab.columns[(size_t)ts[k].virt_col] = hit->cols[k];
+      } else {
+        DFX_RETURN_IF_ERROR(pred_terms.eval(b, &ab));
+        if (term_cache_on && key) {
+          TermCacheEntry e;
+          e.offsets = key;
+          e.rows = n;
+          for (const Utf8TermSpec& t : ts) e.cols.push_back(ab.columns[(size_t)t.virt_col]);
+          term_cache.push_back(std::move(e));
+        }
+      }
     }
     DFX_RETURN_IF_ERROR(builder->bind(ab, &prog, &cols));
   }
@@ -1527,6 +1572,14 @@ Status AggregateRelation::Impl::consume_batch(const DeviceBatch& b) {
     if ((int)held.size() < opt().chunk_hold && held_bytes < ((size_t)8 << 30)) return Status::OK();
     return run_held();
   }
+  struct CacheScope {  // (also left on an error return)
+    Impl& m;
+    explicit CacheScope(Impl& i) : m(i) { m.term_cache_on = true; }
+    ~CacheScope() {
+      m.term_cache_on = false;
+      m.term_cache.clear();
+    }
+  } cache_scope(*this);
   for (int c = 0; c < (int)chunks.size(); ++c) {
     activate(c);
     const int64_t seen = rows_seen;
@@ -1611,6 +1664,14 @@ Status AggregateRelation::Impl::run_held() {
   const int64_t seen = rows_seen;
   int64_t total = 0;
   for (const DeviceBatch& b : hb) total += b.num_rows;
+  term_cache_on = true;  // the string terms' bitmaps: once per held batch, for every chunk
+  struct CacheEnd {
+    Impl& m;
+    ~CacheEnd() {
+      m.term_cache_on = false;
+      m.term_cache.clear();
+    }
+  } cache_end{*this};
   for (int c = 0; c < (int)chunks.size(); ++c) {
     activate(c);
     rows_seen = seen;
@@ -2135,10 +2196,10 @@ AggregateRelation::AggregateRelation(SchemaInfo schema, std::unique_ptr<Relation
       // chunks down to one per program, never below): one that does not would fail the whole query with NotImplemented
       // where the reference -- which has no such limit -- runs it; un-fused, its program holds keys + argument only
       for (size_t a = 0; a < std::max<size_t>(m.aggr.size(), 1) && fits; ++a) {
-        ProgramBuilder trial(f->input()->schema());
+        ProgramBuilder trial(f->program_schema());  // (string terms count as the Boolean columns they become)
         uint8_t opnd = kNoOperand;
         int dt = 0;
-        Status tst = trial.add(f->predicate(), f->predicate().root, &opnd, &dt);
+        Status tst = trial.add(f->program_predicate(), f->program_predicate().root, &opnd, &dt);
         for (size_t k = 0; k < m.group.size() && tst.ok(); ++k)
           if (!m.group[k].is_aggregate) tst = trial.add(m.group[k], m.group[k].root, &opnd, &dt);
         if (tst.ok() && a < m.aggr.size() && m.aggr[a].is_aggregate && m.aggr[a].agg_arg >= 0) tst = trial.add(m.aggr[a], m.aggr[a].agg_arg, &opnd, &dt);
@@ -2164,6 +2225,8 @@ AggregateRelation::AggregateRelation(SchemaInfo schema, std::unique_ptr<Relation
           if (ci >= 0 && ci < (int)needed.size()) needed[ci] = 1;
     for (const Impl::DictKey& d : m.dicts)
       if (d.src_col >= 0 && d.src_col < (int)needed.size()) needed[d.src_col] = 1;
+    for (const Utf8TermSpec& t : m.pred_terms.terms())
+      if (t.src_col >= 0 && t.src_col < (int)needed.size()) needed[t.src_col] = 1;
     m.input->require_columns(needed);
   }
   // output schema: group columns then aggregates (aggregate.rs:894-949); context.rs:185 passes

@@ -17,6 +17,7 @@
 
 #include "../../include/dfx.h"
 #include "dfx_device.hpp"
+#include "dfx_utf8_match.hpp"
 
 namespace dfx {
 
@@ -334,6 +335,44 @@ class ProgramBuilder {
   const SchemaInfo& schema_;
   DevProgram prog_;
   std::vector<int> cols_;
+};
+
+// Utf8 string terms of a predicate (deviation D9; dfx_expr.cpp).  A string term -- `Utf8 column <op> Utf8 literal` for Eq ..
+// GtEq with the literal on either side, `Utf8 column LIKE / NOT LIKE Utf8 literal` -- is evaluated by a kernel of its own
+// (dfx_k_utf8pred.hip) into a bitmap that the fused program reads as a VIRTUAL Boolean column appended after the input
+// schema's columns: the device-dictionary mechanism of Utf8 GROUP BY keys applied to predicates.  Identical terms share a column.
+struct Utf8TermSpec {
+  int src_col = -1;   // the Utf8 column of the input schema
+  int virt_col = -1;  // its Boolean column in the extended schema
+  int op = 0;         // dfx_operator, mirrored when the literal stood on the left
+  Utf8Term term;
+  std::vector<uint8_t> image;  // what the kernel stages: literal bytes padded to 4, then the segment table
+  std::string literal;         // as written
+  std::shared_ptr<void> dev;   // `image` on the device (uploaded with the first batch)
+};
+// is node idx a string term over `schema`?  (*col_left: the column is the left operand)
+bool utf8_string_term(const std::vector<dfx_expr_node>& nodes, int32_t idx, const SchemaInfo& schema, bool* col_left);
+// one term compiled on the host: class, segment table, what a null gives.  op: Eq .. GtEq (column on the left), Like, NotLike
+Status utf8_compile_term(int op, const char* literal, size_t len, Utf8Term* t, std::vector<uint8_t>* image);
+class Utf8Terms {
+ public:
+  // finds the string terms of `e` over `schema`; their virtual columns are numbered from first_virt
+  Status compile(const dfx_runtime_expr& e, const SchemaInfo& schema, int first_virt);
+  bool empty() const { return terms_.empty(); }
+  bool whole() const { return whole_; }  // the predicate IS one term: its bitmap is the mask
+  const dfx_runtime_expr& rewritten() const { return rw_; }  // the predicate with every term replaced by its Boolean column
+  const std::vector<Utf8TermSpec>& terms() const { return terms_; }
+  void append_fields(SchemaInfo* s) const;
+  // launches the term kernels over `in` on the library's stream; ext = in + the virtual columns (ext may hold other virtual
+  // columns already: it is grown, never shrunk)
+  Status eval(const DeviceBatch& in, DeviceBatch* ext);
+  bool source_has_nulls(const DeviceBatch& in) const;
+  std::string explain() const;
+
+ private:
+  std::vector<Utf8TermSpec> terms_;
+  dfx_runtime_expr rw_;
+  bool whole_ = false;
 };
 
 }  // namespace dfx

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "dfx_device.hpp"
+#include "dfx_utf8_match.hpp"
 
 namespace dfx {
 
@@ -32,6 +33,7 @@ enum KernelId : int {
   KID_SORT,
   KID_DISTINCT_INSERT,
   KID_DISTINCT_COUNT,
+  KID_UTF8_PRED,
   KID_COUNT_
 };
 const char* kernel_name(int kid);
@@ -152,6 +154,19 @@ hipError_t launch_dict_remap_plane(uint64_t* plane, uint64_t n_slots, const uint
 hipError_t launch_dict_lengths(const uint64_t* ids, int64_t g, const DevDict& D, uint32_t* lens, hipStream_t s);
 hipError_t launch_dict_gather(const uint64_t* ids, int64_t g, const DevDict& D, const uint64_t* starts, int32_t* offsets,
                               uint8_t* out, hipStream_t s);
+
+// Utf8 string terms (dfx_k_utf8pred.hip, deviation D9): one compiled term (dfx_utf8_match.hpp) over one Utf8 column -> Arrow LSB
+// bitmap, (n + 63) / 64 whole words (bits past n are zero).  T.lit: DEVICE buffer of utf8_term_image_bytes(T.t) bytes (dfx_utf8_match.hpp:
+// the literal bytes, padded to 4, then the segment table).  validity may be null.  Every load stays inside the bytes the batch
+// references, data + [offsets[0], offsets[n]).
+struct DevUtf8Pred {
+  Utf8Term t;
+  const uint8_t* lit;
+};
+hipError_t launch_utf8_pred(const int32_t* offsets, const uint8_t* data, const uint8_t* validity, int64_t bit_offset, int64_t n,
+                            const DevUtf8Pred& T, uint64_t* mask_words, double algo_bytes, hipStream_t s);
+// popcount per 4096-row tile of a finished bitmap (the compaction offsets of a filter whose mask is one term's bitmap)
+hipError_t launch_mask_tile_counts(const uint64_t* mask_words, uint32_t* tile_counts, int64_t n, hipStream_t s);
 
 // partitioned GROUP BY (dfx_k_partition.hip): pass 1 routes passing rows to per-(producer, partition)
 // regions, pass 2 aggregates every partition in an LDS copy of its table block.  Single-word keys.

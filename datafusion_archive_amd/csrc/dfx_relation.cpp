@@ -746,9 +746,12 @@ Status adopt_input_stream(struct ArrowArrayStream* input, std::unique_ptr<Relati
 FilterRelation::FilterRelation(std::unique_ptr<Relation> input, const dfx_runtime_expr& expr, SchemaInfo schema, OptionOverrides options)
     : input_(std::move(input)), expr_(expr), schema_(std::move(schema)) {
   opt_.overrides = std::move(options);
-  builder_.reset(new ProgramBuilder(input_->schema()));
+  prog_schema_ = input_->schema();
+  const Status terms_st = terms_.compile(expr_, input_->schema(), (int)prog_schema_.fields.size());
+  terms_.append_fields(&prog_schema_);
+  builder_.reset(new ProgramBuilder(prog_schema_));
   int dt = DFX_TYPE_NONE;
-  deferred_ = builder_->add(expr_, expr_.root, &pred_operand_, &dt);
+  deferred_ = terms_st.ok() ? builder_->add(program_predicate(), program_predicate().root, &pred_operand_, &dt) : terms_st;
   if (deferred_.ok() && dt != DFX_BOOLEAN)  // filter.rs:64-66
     deferred_ = Status::Err(DFX_EXECUTION_ERROR, "Filter expression did not evaluate to boolean");
   memset(&fast_, 0, sizeof(fast_));
@@ -759,14 +762,15 @@ FilterRelation::FilterRelation(std::unique_ptr<Relation> input, const dfx_runtim
 // the predicate does not fit one fused program: split its top-level AND chain
 Status FilterRelation::build_parts() {
   const Status whole = deferred_;
+  const dfx_runtime_expr& pe = program_predicate();  // (string terms are Boolean columns here)
   std::vector<int32_t> conj;  // roots of the conjuncts, left to right
   {
-    std::vector<int32_t> stack{expr_.root};
+    std::vector<int32_t> stack{pe.root};
     while (!stack.empty()) {
       const int32_t at = stack.back();
       stack.pop_back();
-      if (at < 0 || at >= (int32_t)expr_.nodes.size()) return whole;
-      const dfx_expr_node& n = expr_.nodes[(size_t)at];
+      if (at < 0 || at >= (int32_t)pe.nodes.size()) return whole;
+      const dfx_expr_node& n = pe.nodes[(size_t)at];
       if (n.kind == DFX_EXPR_BINARY && n.op == DFX_OP_AND) {
         stack.push_back(n.right);
         stack.push_back(n.left);
@@ -778,7 +782,7 @@ Status FilterRelation::build_parts() {
   if (conj.size() < 2) return whole;  // nothing to split (one oversized comparison / OR tree)
   // AND chain over conj[from, to) as an expression of its own (the original nodes plus the new AND nodes)
   auto chain = [&](size_t from, size_t to) {
-    dfx_runtime_expr e = expr_;
+    dfx_runtime_expr e = pe;
     int32_t root = conj[from];
     for (size_t i = from + 1; i < to; ++i) {
       dfx_expr_node a;
@@ -805,7 +809,7 @@ Status FilterRelation::build_parts() {
     size_t best_to = from;
     for (size_t to = from + 1; to <= conj.size(); ++to) {  // the longest prefix of the remaining conjuncts that fits
       Part p;
-      p.builder.reset(new ProgramBuilder(input_->schema()));
+      p.builder.reset(new ProgramBuilder(prog_schema_));
       memset(&p.fast, 0, sizeof(p.fast));
       const dfx_runtime_expr e = chain(from, to);
       int dt = DFX_TYPE_NONE;
@@ -845,7 +849,10 @@ void FilterRelation::explain(std::string* out, int depth) const {
                                                                  : "mask + scan + compaction (two passes over the predicate's columns), ") +
                                  explain_program(P) + ", " + shape +
                                  (out_needed_.empty() ? std::string(", every column compacted") : strfmt(", %d columns compacted", n)) +
-                                 (more_.empty() ? std::string() : strfmt(", conjunction evaluated by %zu fused programs (masks ANDed)", more_.size() + 1)));
+                                 (more_.empty() ? std::string() : strfmt(", conjunction evaluated by %zu fused programs (masks ANDed)", more_.size() + 1)) +
+                                 (terms_.empty() ? std::string()
+                                                 : std::string(terms_.whole() ? "; the predicate is one Utf8 string term, its bitmap is the mask (no program runs): "
+                                                                              : "; Utf8 string terms evaluated per batch into virtual Boolean columns: ") + terms_.explain()));
   }
   if (input_) input_->explain(out, depth + 1);
 }
@@ -861,6 +868,8 @@ void FilterRelation::require_columns(const std::vector<char>& needed) {
   for (const Part& p : more_)
     for (int ci : p.builder->columns())
       if (ci >= 0 && ci < (int)in_needed.size()) in_needed[ci] = 1;
+  for (const Utf8TermSpec& t : terms_.terms())  // a string term's Utf8 column, although nobody may project it
+    if (t.src_col >= 0 && t.src_col < (int)in_needed.size()) in_needed[t.src_col] = 1;
   input_->require_columns(in_needed);
 }
 
@@ -899,15 +908,26 @@ Status FilterRelation::next(DeviceBatch* out, bool* has) {
     *has = true;
     return Status::OK();
   }
+  // Utf8 string terms first, on the same stream: their bitmaps are bound as virtual Boolean columns after the input's own
+  // (`in` stays what the output and fn filter's Boolean check see)
+  DeviceBatch ext;
+  if (!terms_.empty()) DFX_RETURN_IF_ERROR(terms_.eval(in, &ext));
+  const DeviceBatch& pin = terms_.empty() ? in : ext;
+  const bool term_is_mask = terms_.whole() && more_.empty();  // the predicate is one string term: no program runs
   DevProgram prog;
   DevColumns cols;
-  DFX_RETURN_IF_ERROR(builder_->bind(in, &prog, &cols));
+  memset(&prog, 0, sizeof(prog));
+  memset(&cols, 0, sizeof(cols));
+  if (!term_is_mask) DFX_RETURN_IF_ERROR(builder_->bind(pin, &prog, &cols));
   if (!ctrl_) DFX_RETURN_IF_ERROR(alloc_zeroed_ctrl(&ctrl_));
   const int64_t n_words = (n + 63) / 64;
   const int64_t n_tiles = (n + kTileRows - 1) / kTileRows;
   Status st;
-  auto mask = device_alloc(sizeof(uint64_t) * (size_t)n_words, &st);
-  if (!mask) return st;
+  std::shared_ptr<void> mask;
+  if (!term_is_mask) {  // (a one-term predicate brings its own bitmap)
+    mask = device_alloc(sizeof(uint64_t) * (size_t)n_words, &st);
+    if (!mask) return st;
+  }
   auto counts = device_alloc(sizeof(uint32_t) * (size_t)n_tiles, &st);
   if (!counts) return st;
   auto offsets = device_alloc(sizeof(uint64_t) * (size_t)(n_tiles + 1), &st);
@@ -915,7 +935,7 @@ Status FilterRelation::next(DeviceBatch* out, bool* has) {
   auto tmp = device_alloc(sizeof(uint64_t) * (size_t)(n_tiles / 4096 + 4), &st);
   if (!tmp) return st;
   double in_bytes = (double)n / 8.0;
-  for (int ci : builder_->columns()) in_bytes += (double)n * (in.columns[ci].dtype == DFX_BOOLEAN ? 0.125 : dtype_width(in.columns[ci].dtype));
+  for (int ci : builder_->columns()) in_bytes += (double)n * (pin.columns[ci].dtype == DFX_BOOLEAN ? 0.125 : dtype_width(pin.columns[ci].dtype));
   DevFastPlan fp = fast_;
   if (!opt_.get().fast) fp.valid = 0;
   uint64_t kept = 0;
@@ -925,7 +945,16 @@ Status FilterRelation::next(DeviceBatch* out, bool* has) {
   std::vector<std::shared_ptr<void>> fused_vals(in.columns.size());
   bool any_boolean = false;
   for (size_t c = 0; c < in.columns.size(); ++c) any_boolean = any_boolean || in.columns[c].dtype == DFX_BOOLEAN;
-  if (more_.empty() && opt_.get().filter_single_pass) {
+  if (term_is_mask) {
+    // the whole predicate is one string term: its bitmap IS the mask -- tile counts, scan and compaction take it as it is.
+    // (sel_seen_ is left alone: it sizes the output buffers of the fused single-pass kernel, which never runs for such a predicate)
+    mask = ext.columns[(size_t)terms_.terms()[0].virt_col].owners[0];
+    DFX_HIP(launch_mask_tile_counts((const uint64_t*)mask.get(), (uint32_t*)counts.get(), n, s));
+    DFX_HIP(launch_scan_u32((const uint32_t*)counts.get(), (uint64_t*)offsets.get(), n_tiles, (uint64_t*)tmp.get(), s));
+    DFX_HIP(hipMemcpyAsync(&kept, (uint64_t*)offsets.get() + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    DFX_HIP(hipStreamSynchronize(s));
+    single_pass_done = true;
+  } else if (more_.empty() && opt_.get().filter_single_pass) {
     // SINGLE PASS: predicate, bitmap, tile offsets (decoupled look-back) and the compaction of up to kFusedOutCols of
     // the predicate's own columns in one kernel -- such a column is read from HBM once (filter.rs:46-110)
     DevFusedOut O;
@@ -1005,9 +1034,9 @@ Status FilterRelation::next(DeviceBatch* out, bool* has) {
       for (const Part& p : more_) {
         DevProgram prog2;
         DevColumns cols2;
-        DFX_RETURN_IF_ERROR(p.builder->bind(in, &prog2, &cols2));
+        DFX_RETURN_IF_ERROR(p.builder->bind(pin, &prog2, &cols2));
         double bytes2 = (double)n / 8.0;
-        for (int ci : p.builder->columns()) bytes2 += (double)n * (in.columns[ci].dtype == DFX_BOOLEAN ? 0.125 : dtype_width(in.columns[ci].dtype));
+        for (int ci : p.builder->columns()) bytes2 += (double)n * (pin.columns[ci].dtype == DFX_BOOLEAN ? 0.125 : dtype_width(pin.columns[ci].dtype));
         DevFastPlan fp2 = p.fast;
         if (!opt_.get().fast) fp2.valid = 0;
         DFX_HIP(launch_predicate_mask(prog2, fp2, cols2, p.operand, n, (uint64_t*)mask2.get(), nullptr, (uint32_t*)ctrl_.get(), bytes2, s));

@@ -163,6 +163,10 @@ class FilterRelation : public Relation {
   // for Filter -> Aggregate fusion
   std::unique_ptr<Relation> release_input() { return std::move(input_); }
   const dfx_runtime_expr& predicate() const { return expr_; }
+  // what the fused program is built from: the predicate with its Utf8 string terms (deviation D9) replaced by virtual Boolean
+  // columns, over the input schema extended by those columns
+  const dfx_runtime_expr& program_predicate() const { return terms_.empty() ? expr_ : terms_.rewritten(); }
+  const SchemaInfo& program_schema() const { return prog_schema_; }
   Relation* input() { return input_.get(); }
   bool single_program() const { return more_.empty(); }  // false: the predicate is evaluated as several conjuncts
   // test hook (dfx_filter_debug_mask): keep the bitmap of the most recent input batch
@@ -174,6 +178,8 @@ class FilterRelation : public Relation {
   std::unique_ptr<Relation> input_;
   dfx_runtime_expr expr_;
   SchemaInfo schema_;
+  Utf8Terms terms_;          // the predicate's string terms: a kernel of their own per batch, bound as virtual Boolean columns
+  SchemaInfo prog_schema_;   // input schema + those columns (what the programs bind to; never part of the output)
   std::unique_ptr<ProgramBuilder> builder_;
   uint8_t pred_operand_ = kNoOperand;
   DevFastPlan fast_;

@@ -178,6 +178,12 @@ class Expr:
     def or_(self, other: "Expr") -> "Expr":
         return BinaryExpr(self, Operator.Or, other)
 
+    def like(self, pattern: "Expr") -> "Expr":
+        return BinaryExpr(self, Operator.Like, pattern)
+
+    def not_like(self, pattern: "Expr") -> "Expr":
+        return BinaryExpr(self, Operator.NotLike, pattern)
+
     def plus(self, other: "Expr") -> "Expr":
         return BinaryExpr(self, Operator.Plus, other)
 

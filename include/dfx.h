@@ -190,6 +190,14 @@ int32_t dfx_synchronize(char* err, size_t errlen);
  * unsupported aggregate :103-106).
  * Aggregate names (matched case-insensitively): MIN, MAX, SUM, COUNT, AVG and COUNT_DISTINCT (one argument, return type
  * UInt64: the number of distinct non-null argument values; a Rust shim maps AggregateType::CountDistinct to this name).
+ * Utf8 string terms (deviation D9): a BinaryExpr of a bare Utf8 Column and a Utf8 Literal compiles -- Eq NotEq Lt LtEq Gt GtEq
+ * with the literal on either side, Like / NotLike with the column on the left and the pattern on the right -- to a Boolean
+ * expression named by its Debug form (`#4 Eq Utf8("CO")`), alone or anywhere under AND / OR beside numeric terms.  Ordering is
+ * Rust `str` ordering (unsigned byte-wise, a proper prefix first), equality is byte equality.  LIKE: `%` any run of bytes, `_`
+ * one UTF-8 encoded character, no escape character, anchored at both ends; NOT LIKE is the complement on non-null rows.  A null
+ * slot gives Eq false, NotEq true, Lt / LtEq true, Gt / GtEq false, Like false, NotLike true (arrow 0.12 bool_op over
+ * Option<T>; recalled, unpinned).  A literal of more than 4096 bytes is DFX_NOT_IMPLEMENTED.  Every other use of a Utf8
+ * literal, Like on other operands and Utf8 column against Utf8 column are refused as the reference refuses them.
  * ---------------------------------------------------------------------------------------- */
 typedef struct dfx_runtime_expr dfx_runtime_expr;
 
@@ -400,6 +408,11 @@ uint32_t dfx_debug_unhash32(uint32_t image);
  * is null (arrow 0.12's rule for None decides).  Returns 0 / 1, or -1 for a type the plans do not cover.  Host code, no
  * GPU needed: the CPU tests compare it with the comparison it restates over NaN, +-0.0, +-inf and the integer extremes. */
 int32_t dfx_debug_plan_term(int32_t dtype, int32_t op, uint64_t literal, uint64_t value, int32_t is_null);
+/* Debug: one Utf8 string term (deviation D9, see dfx_compile_scalar_expr) over ONE value, evaluated on the host by the matcher
+ * the term kernel runs per row (csrc/dfx_utf8_match.hpp).  op: DFX_OP_EQ .. DFX_OP_GT_EQ with the value on the left, DFX_OP_LIKE
+ * or DFX_OP_NOT_LIKE; literal: the NUL-terminated literal / pattern; value, value_len: the value's bytes; is_null: the value is
+ * null.  Returns 0 / 1, or -1 for a bad call (another operator, a null pointer, a literal of more than 4096 bytes).  No GPU needed. */
+int32_t dfx_debug_utf8_term(int32_t op, const char* literal, const uint8_t* value, int64_t value_len, int32_t is_null);
 /* Pulls every batch of a library stream and drops it on the device: no host RecordBatch, no D2H copy (what a stacked
  * operator would see).  rows / batches (may be NULL): what came out. */
 int32_t dfx_relation_drain_device(struct ArrowArrayStream* stream, int64_t* rows, int64_t* batches, char* err, size_t errlen);

@@ -297,6 +297,8 @@ fn flatten(e: &Expr, out: &mut Vec<DfxExprNode>, names: &mut Vec<CString>) -> i3
                 ScalarValue::Float32(x) => { n.dtype = 10; n.lit = x.to_bits() as u64; }
                 ScalarValue::Float64(x) => { n.dtype = 11; n.lit = x.to_bits(); }
                 ScalarValue::Utf8(s) => {
+                    // a literal node like the others: the library accepts it as an operand of a string term
+                    // (Utf8 column <op> literal, LIKE / NOT LIKE: deviation D9) and refuses it anywhere else
                     n.dtype = 12;
                     names.push(CString::new(s.as_str()).unwrap());
                     n.name = names.last().unwrap().as_ptr();

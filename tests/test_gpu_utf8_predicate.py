@@ -1,0 +1,431 @@
+"""GPU tests of Utf8 string terms (deviation D9) through the C ABI.  Expected results never come from this library: the expected
+mask is computed in Python (`bytes` comparison, a translation of LIKE to `re` over `str`, the null rule of arrow 0.12's
+bool_op), and filters / aggregates are compared bit for bit with the CPU oracle running the same query with the string
+predicate replaced by `m = 1` over a helper Int32 column `m` that holds the Python mask (the GPU sees the same schema and
+ignores `m`)."""
+import os
+import random
+import re
+
+import numpy as np
+import pyarrow as pa
+import pytest
+
+import oracle
+from datafusion_archive_amd import execution as ex
+from datafusion_archive_amd.logicalplan import AggregateFunction, BinaryExpr, Cast, Column, DataType, Literal, Operator, ScalarValue
+from fixtures import DATA, load_csv, uk_cities_schema
+from gpu_util import assert_batches_identical, assert_groups_identical
+
+pytestmark = pytest.mark.gpu
+
+utf8 = lambda s: Literal(ScalarValue.Utf8(s))
+i32 = lambda v: Literal(ScalarValue.Int32(v))
+i64 = lambda v: Literal(ScalarValue.Int64(v))
+f64 = lambda v: Literal(ScalarValue.Float64(v))
+B = BinaryExpr
+CMP = {Operator.Eq: lambda a, b: a == b, Operator.NotEq: lambda a, b: a != b, Operator.Lt: lambda a, b: a < b,
+       Operator.LtEq: lambda a, b: a <= b, Operator.Gt: lambda a, b: a > b, Operator.GtEq: lambda a, b: a >= b}
+ALL_OPS = list(CMP) + [Operator.Like, Operator.NotLike]
+NULL_GIVES = {Operator.Eq: False, Operator.NotEq: True, Operator.Lt: True, Operator.LtEq: True, Operator.Gt: False, Operator.GtEq: False,
+              Operator.Like: False, Operator.NotLike: True}
+
+
+def like_regex(pattern: str):
+    out, run = [], []
+    for ch in pattern:
+        if ch in "%_":
+            out.append(re.escape("".join(run)))
+            run = []
+            out.append(".*" if ch == "%" else ".")
+        else:
+            run.append(ch)
+    out.append(re.escape("".join(run)))
+    return re.compile("".join(out), re.DOTALL)
+
+
+def sterm(op, literal, value):
+    """One string term over one value (None: null), stated independently of the library."""
+    if value is None:
+        return NULL_GIVES[op]
+    if op in CMP:
+        return CMP[op](value.encode(), literal.encode())
+    m = like_regex(literal).fullmatch(value) is not None
+    return m if op == Operator.Like else not m
+
+
+def term_mask(op, literal, values):
+    """The same over a list of values; distinct values are evaluated once."""
+    memo = {}
+    out = np.zeros(len(values), dtype=bool)
+    for i, v in enumerate(values):
+        if v not in memo:
+            memo[v] = sterm(op, literal, v)
+        out[i] = memo[v]
+    return out
+
+
+def with_mask(batch: pa.RecordBatch, mask: np.ndarray):
+    """batch + the helper column `m`; returns (batch, the oracle's predicate `m = 1`)"""
+    b = batch.append_column(pa.field("m", pa.int32(), False), pa.array(mask.astype(np.int32), pa.int32()))
+    return b, B(Column(b.num_columns - 1), Operator.Eq, i32(1))
+
+
+def check_filter(batches, masks, pred, what, options=None, project=None):
+    """FilterRelation over `batches` (which carry `m`): bitmap == the Python mask, output == the oracle's Filter(m = 1)."""
+    schema = batches[0].schema
+    rel = ex.FilterRelation(ex.DataSourceRelation(schema, batches), ex.compile_scalar_expr(None, pred, schema), schema, options)
+    rel.keep_mask()
+    mpred = B(Column(schema.get_field_index("m")), Operator.Eq, i32(1))
+    for i, (b, m) in enumerate(zip(batches, masks)):
+        got = rel.next()
+        assert got is not None, f"{what}: batch {i} missing"
+        if b.num_rows:
+            bits, rows = rel.last_mask(b.num_rows)
+            assert rows == b.num_rows
+            want_bits = np.packbits(m, bitorder="little")
+            bad = np.nonzero(bits != want_bits)[0]
+            assert bad.size == 0, f"{what}: batch {i}: bitmap differs first at byte {bad[:1]} (rows {bad[:1] * 8}..)"
+        assert_batches_identical(got, oracle.filter_next(mpred, b), f"{what} batch {i}")
+    assert rel.next() is None
+    return rel
+
+
+# ---- the reference's fixtures -------------------------------------------------------------------------------------------------
+# ('%Scotland%': the one such city is the file's first line, which the reader drops as a header -- an empty result)
+UK_PREDS = [(Operator.Eq, "Solihull, Birmingham, UK"), (Operator.Like, "%Scotland%"), (Operator.Lt, "M"), (Operator.Like, "%Birmingham%")]
+
+
+@pytest.mark.parametrize("op,literal", UK_PREDS)
+def test_uk_cities_from_arrow_batches(op, literal):
+    b = load_csv("uk_cities.csv", uk_cities_schema())[0]
+    cities = b.column(0).to_pylist()
+    mask = term_mask(op, literal, cities)
+    assert mask.sum() == sum(1 for c in cities if sterm(op, literal, c)) and mask.sum() < len(cities)
+    bm, _ = with_mask(b, mask)
+    check_filter([bm], [mask], B(Column(0), op, utf8(literal)), f"uk_cities {op.name} {literal!r}")
+
+
+@pytest.mark.parametrize("fixture,schema,col,op,literal", [
+    ("uk_cities.csv", uk_cities_schema(), 0, Operator.Eq, "Solihull, Birmingham, UK"),
+    ("uk_cities.csv", uk_cities_schema(), 0, Operator.Like, "%Scotland%"),
+    ("uk_cities.csv", uk_cities_schema(), 0, Operator.Lt, "M"),
+    ("uk_cities.csv", uk_cities_schema(), 0, Operator.Like, "%Birmingham%"),
+    ("people.csv", pa.schema([("id", pa.int64()), ("first_name", pa.string())]), 1, Operator.GtEq, "B"),
+])
+def test_fixtures_from_csv_text_parsed_on_the_device(fixture, schema, col, op, literal):
+    path = os.path.join(DATA, fixture)
+    rows = pa.Table.from_batches(oracle.read_csv(path, schema, 1024))
+    mask = term_mask(op, literal, rows.column(col).to_pylist())
+    pred = ex.compile_scalar_expr(None, B(Column(col), op, utf8(literal)), schema)
+    got = pa.Table.from_batches(list(ex.FilterRelation(ex.CsvDataSource(path, schema, 1024), pred, schema)))
+    want = rows.filter(pa.array(mask))
+    assert got.num_rows == want.num_rows
+    for c in range(want.num_columns):
+        assert got.column(c).to_pylist() == want.column(c).to_pylist()
+    # and from Arrow batches of the same rows
+    b = rows.combine_chunks().to_batches()[0]
+    bm, _ = with_mask(b, mask)
+    check_filter([bm], [mask], B(Column(col), op, utf8(literal)), fixture)
+
+
+# ---- the planner's own example ------------------------------------------------------------------------------------------------
+def person_rows():
+    rng = random.Random(570)
+    n = 200
+    return {"id": pa.array(range(n), pa.uint32()), "first_name": [rng.choice(["Ann", "Bob", "Cy"]) for _ in range(n)],
+            "last_name": [rng.choice(["Smith", "Jones"]) for _ in range(n)], "age": pa.array([rng.randrange(10, 90) for _ in range(n)], pa.int32()),
+            "state": [rng.choice(["CO", "CA", "C", "COO", "NY", ""]) for _ in range(n)], "salary": [float(rng.randrange(1000)) for _ in range(n)]}
+
+
+def test_person_state_eq_co_and_the_compound_selection():
+    cols = person_rows()
+    state_co = B(Column(4), Operator.Eq, utf8("CO"))
+    run_filter(py_typed(cols), [64], state_co, lambda r: r["state"] == "CO", "state = 'CO'")
+    age = Cast(Column(3), DataType.Int64)
+    compound = B(B(state_co, Operator.And, B(age, Operator.GtEq, i64(21))), Operator.And, B(age, Operator.LtEq, i64(65)))  # sqlplanner.rs:581
+    run_filter(py_typed(cols), [64], compound, lambda r: r["state"] == "CO" and 21 <= r["age"] <= 65, "compound selection")
+
+
+def py_typed(cols):
+    """name -> list of python values for the mask, arrays kept for the batch"""
+    t = TypedCols()
+    for k, v in cols.items():
+        t.add(k, v)
+    return t
+
+
+class TypedCols(dict):
+    """dict of python lists (what pymask reads) that remembers the Arrow arrays the batch is built from"""
+
+    def __init__(self):
+        super().__init__()
+        self.arrays = {}
+
+    def add(self, k, v):
+        self.arrays[k] = v if isinstance(v, pa.Array) else pa.array(v)
+        self[k] = self.arrays[k].to_pylist()
+
+
+def run_typed(t: TypedCols, bounds, pred, pymask, what, options=None):
+    names = list(t)
+    n = len(t[names[0]])
+    mask = np.array([bool(pymask({k: t[k][r] for k in names})) for r in range(n)], dtype=bool)
+    full, _ = with_mask(pa.RecordBatch.from_arrays([t.arrays[k] for k in names], names=names), mask)
+    edges = [0] + list(bounds) + [n]
+    batches = [full.slice(a, b - a) for a, b in zip(edges[:-1], edges[1:])]
+    masks = [mask[a:b] for a, b in zip(edges[:-1], edges[1:])]
+    return check_filter(batches, masks, pred, what, options), batches, mask
+
+
+def run_filter(cols, bounds, pred, pymask, what, options=None):
+    t = cols if isinstance(cols, TypedCols) else py_typed(cols)
+    return run_typed(t, bounds, pred, pymask, what, options)[0]
+
+
+# ---- all operators x lengths ---------------------------------------------------------------------------------------------------
+LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 300]
+
+
+def make_strings(rng, n, lengths, nulls=False):
+    """values of the given byte lengths with shared prefixes and multi-byte characters; a pool, so that literals hit"""
+    pool = []
+    for ln in lengths:
+        base = ("prefix-é-" * (ln // 9 + 1))
+        for tail in ("a", "b", "é", ""):
+            s = (base + tail * 3).encode()[:ln]
+            while True:  # cut on a character boundary
+                try:
+                    pool.append(s.decode())
+                    break
+                except UnicodeDecodeError:
+                    s = s[:-1]
+    vals = [rng.choice(pool) for _ in range(n)]
+    if nulls:
+        vals = [None if rng.random() < 0.2 else v for v in vals]
+    return vals, pool
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
+def test_all_operators_over_lengths(n):
+    rng = random.Random(n)
+    vals, pool = make_strings(rng, n, LENGTHS)
+    t = py_typed({"s": pa.array(vals, pa.string()), "x": pa.array(range(n), pa.int32())})
+    for ln in LENGTHS:
+        literal = next(p for p in pool if len(p.encode()) >= ln - 1 and len(p.encode()) <= ln)
+        for op in ALL_OPS:
+            run_filter(t, [], B(Column(0), op, utf8(literal)), lambda r: sterm(op, literal, r["s"]), f"n={n} {op.name} len {ln}")
+    for op in list(CMP):  # the literal on the left mirrors the operator
+        literal = pool[5]
+        run_filter(t, [], B(utf8(literal), op, Column(0)), lambda r: CMP[op](literal.encode(), r["s"].encode()), f"n={n} literal {op.name} column")
+
+
+def test_nulls_ragged_batches_and_slices():
+    rng = random.Random(9)
+    n = 3000
+    vals, pool = make_strings(rng, n, LENGTHS, nulls=True)
+    t = py_typed({"s": pa.array(vals, pa.string()), "x": pa.array(range(n), pa.int32())})
+    for op in ALL_OPS:
+        for literal in (pool[9], "prefix-%", "%é-a%", "%b", "p_efix-_-%a"):
+            if op in CMP and "%" in literal:
+                continue
+            # three ragged batches, a zero-row batch, and (all of them but the first) slices with non-zero offsets
+            run_filter(t, [1000, 1000, 1937], B(Column(0), op, utf8(literal)), lambda r: sterm(op, literal, r["s"]), f"nulls {op.name} {literal!r}")
+
+
+def test_long_strings_take_the_wave_per_row_path():
+    """every string longer than a tile's LDS share (64 rows x > 64 bytes), 5000-byte values and literals"""
+    rng = random.Random(5000)
+    base = "".join(rng.choice("abé") for _ in range(5200))
+    cut = lambda s, ln: s.encode()[:ln].decode(errors="ignore")
+    vals = []
+    for i in range(200):
+        ln = rng.choice([300, 4096, 5000])
+        v = cut(base, ln)
+        if i % 3 == 0:
+            v = v[:-2] + rng.choice(["a", "zz", ""])
+        if i % 7 == 0:
+            v = rng.choice(["b", "a"]) + v[1:]
+        vals.append(v)
+    t = py_typed({"s": pa.array(vals, pa.string())})
+    lit = cut(base, 4096)
+    for op in list(CMP):
+        for literal in (lit, cut(base, 300), cut(vals[3], 4000)):
+            run_filter(t, [70], B(Column(0), op, utf8(literal)), lambda r: sterm(op, literal, r["s"]), f"long {op.name}")
+    for literal in (cut(base, 300) + "%", "%" + cut(base, 300)[-200:], "%" + base[1000:1300] + "%", "%zz", "a%" + base[2000:2100] + "_%", cut(base, 4000) + "%"):
+        for op in (Operator.Like, Operator.NotLike):
+            run_filter(t, [70], B(Column(0), op, utf8(literal)), lambda r: sterm(op, literal, r["s"]), f"long {op.name} {literal[:12]!r}")
+
+
+def test_every_like_class_and_underscore_in_a_middle_segment():
+    rng = random.Random(77)
+    words = ["", "a", "ab", "abc", "abcabc", "xabcx", "éa", "aéb", "a\U0001F600b", "abXcd", "ab12cd34", "cdab", "%", "_"]
+    vals = [rng.choice(words) + rng.choice(words) for _ in range(700)]
+    t = py_typed({"s": pa.array(vals, pa.string())})
+    for literal in ("abc", "", "abc%", "%abc", "%abc%", "%", "%%", "_", "__", "a_b", "a%c", "a%b_c%d", "%a_c%", "ab%_", "%_", "_%_", "%é%", "a_%", "%b%c%"):
+        for op in (Operator.Like, Operator.NotLike):
+            run_filter(t, [], B(Column(0), op, utf8(literal)), lambda r: sterm(op, literal, r["s"]), f"{op.name} {literal!r}")
+
+
+# ---- mixes ---------------------------------------------------------------------------------------------------------------------
+def mix_table(n=5000, seed=3, nulls=False):
+    rng = random.Random(seed)
+    names = ["alpha", "beta", "b", "bz", "c", "gamma", "délta", "be", ""]
+    s = [rng.choice(names) for _ in range(n)]
+    u = [rng.choice(["x", "y", "zz"]) for _ in range(n)]
+    if nulls:
+        s = [None if rng.random() < 0.1 else v for v in s]
+    return py_typed({"s": pa.array(s, pa.string()), "k": pa.array([rng.randrange(7) for _ in range(n)], pa.int32()),
+                     "v": pa.array([rng.randrange(-4096, 4096) / 1024.0 for _ in range(n)], pa.float64()),
+                     "u": pa.array(u, pa.string()), "w": pa.array([rng.randrange(1000) for _ in range(n)], pa.int64())})
+
+
+S, K, V, U, W = Column(0), Column(1), Column(2), Column(3), Column(4)
+MIXES = [
+    ("AND numeric", B(B(S, Operator.Eq, utf8("beta")), Operator.And, B(V, Operator.Gt, f64(0.0))), lambda r: sterm(Operator.Eq, "beta", r["s"]) and r["v"] > 0.0),
+    ("OR numeric", B(B(S, Operator.Like, utf8("b%")), Operator.Or, B(W, Operator.Lt, i64(100))), lambda r: sterm(Operator.Like, "b%", r["s"]) or r["w"] < 100),
+    ("two columns", B(B(S, Operator.GtEq, utf8("c")), Operator.And, B(U, Operator.NotEq, utf8("zz"))), lambda r: sterm(Operator.GtEq, "c", r["s"]) and r["u"] != "zz"),
+    ("range", B(B(S, Operator.GtEq, utf8("b")), Operator.And, B(S, Operator.Lt, utf8("c"))), lambda r: sterm(Operator.GtEq, "b", r["s"]) and sterm(Operator.Lt, "c", r["s"])),
+    ("OR of terms under AND", B(B(B(S, Operator.Eq, utf8("b")), Operator.Or, B(U, Operator.Like, utf8("_"))), Operator.And, B(K, Operator.NotEq, i32(3))),
+     lambda r: (sterm(Operator.Eq, "b", r["s"]) or sterm(Operator.Like, "_", r["u"])) and r["k"] != 3),
+    ("shared term", B(B(B(S, Operator.Eq, utf8("c")), Operator.And, B(W, Operator.Lt, i64(500))), Operator.Or, B(B(S, Operator.Eq, utf8("c")), Operator.And, B(V, Operator.Lt, f64(0.0)))),
+     lambda r: sterm(Operator.Eq, "c", r["s"]) and (r["w"] < 500 or r["v"] < 0.0)),
+]
+
+
+@pytest.mark.parametrize("what,pred,py", MIXES, ids=[m[0] for m in MIXES])
+@pytest.mark.parametrize("nulls", [False, True])
+def test_mixes_with_numeric_terms(what, pred, py, nulls):
+    t = mix_table(nulls=nulls)
+    for options in (None, {"filter.single_pass": 0}):
+        run_filter(t, [2000, 2000, 4097], pred, py, f"{what} nulls={nulls} {options}", options)
+
+
+def test_projection_push_down_and_explain():
+    t = mix_table()
+    _, batches, mask = run_typed(t, [], B(S, Operator.Like, utf8("%a")), lambda r: sterm(Operator.Like, "%a", r["s"]), "")
+    schema = batches[0].schema
+    pred = ex.compile_scalar_expr(None, B(S, Operator.Like, utf8("%a")), schema)
+    filt = ex.FilterRelation(ex.DataSourceRelation(schema, batches), pred, schema)
+    text = ex.explain(filt)
+    assert "one Utf8 string term" in text and "suffix" in text and "#0 Like" in text and "literal of 2 bytes" in text
+    # the predicate's column is not projected: the aggregate reads `w` only
+    got = ex.AggregateRelation(None, filt, [], [ex.compile_expr(None, AggregateFunction("SUM", [W], DataType.Int64), schema)]).next()
+    assert got.column(0).to_pylist() == [int(np.array(t["w"])[mask].sum())]
+
+
+def test_resident_table_scanned_twice():
+    t = mix_table(n=20000)
+    _, batches, mask = run_typed(t, [], B(S, Operator.Lt, utf8("c")), lambda r: sterm(Operator.Lt, "c", r["s"]), "")
+    schema = batches[0].schema
+    table = ex.DeviceTable.from_batches(schema, batches)
+    want = oracle.filter_next(B(Column(5), Operator.Eq, i32(1)), batches[0])
+    for _ in range(2):
+        rel = ex.FilterRelation(table.scan(4096 + 64), ex.compile_scalar_expr(None, B(S, Operator.Lt, utf8("c")), schema), schema)
+        got = pa.Table.from_batches(list(rel)).combine_chunks().to_batches()[0]
+        assert_batches_identical(got, want, "resident table")
+
+
+# ---- aggregates over the filter ---------------------------------------------------------------------------------------------------
+def agg(f, col, dt):
+    return AggregateFunction(f, [col], dt)
+
+
+AGGS = [agg("MIN", V, DataType.Float64), agg("MAX", V, DataType.Float64), agg("SUM", V, DataType.Float64), agg("COUNT", W, DataType.UInt64),
+        agg("SUM", W, DataType.Int64)]
+
+
+def check_aggregate(t, bounds, group, aggs, pred, py, what):
+    _, batches, mask = run_typed(t, bounds, pred, py, what)
+    schema = batches[0].schema
+    mpred = B(Column(schema.get_field_index("m")), Operator.Eq, i32(1))
+    want = oracle.aggregate(group, aggs, [oracle.filter_next(mpred, b) for b in batches])
+    rel = ex.FilterRelation(ex.DataSourceRelation(schema, batches), ex.compile_scalar_expr(None, pred, schema), schema)
+    rel = ex.AggregateRelation(None, rel, [ex.compile_scalar_expr(None, g, schema) for g in group], [ex.compile_expr(None, a, schema) for a in aggs])
+    got = rel.next()
+    assert got is not None and rel.next() is None
+    if group:
+        assert_groups_identical(got, want, len(group), what)
+    else:
+        assert_batches_identical(got, want, what)
+
+
+@pytest.mark.parametrize("nulls", [False, True])
+def test_aggregates_over_string_predicates(nulls):
+    t = mix_table(n=30000, nulls=nulls)
+    like_b = (B(S, Operator.Like, utf8("b%")), lambda r: sterm(Operator.Like, "b%", r["s"]))
+    mixed = (B(B(S, Operator.NotEq, utf8("gamma")), Operator.And, B(V, Operator.Gt, f64(-1.0))), lambda r: sterm(Operator.NotEq, "gamma", r["s"]) and r["v"] > -1.0)
+    under_or = (B(B(S, Operator.Eq, utf8("alpha")), Operator.Or, B(W, Operator.Lt, i64(50))), lambda r: sterm(Operator.Eq, "alpha", r["s"]) or r["w"] < 50)
+    for name, (pred, py) in (("like", like_b), ("mixed", mixed), ("or", under_or)):
+        check_aggregate(t, [10000, 20001], [], AGGS, pred, py, f"ungrouped {name} nulls={nulls}")
+        check_aggregate(t, [10000, 20001], [K], AGGS, pred, py, f"by Int key {name} nulls={nulls}")
+        if not nulls:  # (the key column itself: the dictionary has no null key)
+            check_aggregate(t, [10000, 20001], [S], AGGS, pred, py, f"by the predicate's Utf8 column {name}")
+    # COUNT_DISTINCT (the oracle has none): counted in Python over the oracle's Filter(m = 1) output
+    cd = [agg("COUNT_DISTINCT", W, DataType.UInt64), agg("COUNT_DISTINCT", U, DataType.UInt64), agg("SUM", W, DataType.Int64)]
+    for group, (pred, py) in (([K], like_b), ([], mixed)):
+        _, batches, _ = run_typed(t, [10000, 20001], pred, py, "COUNT_DISTINCT")
+        schema = batches[0].schema
+        mpred = B(Column(schema.get_field_index("m")), Operator.Eq, i32(1))
+        rows = pa.Table.from_batches([oracle.filter_next(mpred, b) for b in batches]).to_pydict()
+        want = {}
+        for k, w, u in zip(rows["k"] if group else [0] * len(rows["w"]), rows["w"], rows["u"]):
+            e = want.setdefault(k, [set(), set(), 0])
+            e[0].add(w), e[1].add(u)
+            e[2] += w
+        rel = ex.FilterRelation(ex.DataSourceRelation(schema, batches), ex.compile_scalar_expr(None, pred, schema), schema)
+        got = ex.AggregateRelation(None, rel, [ex.compile_scalar_expr(None, g, schema) for g in group], [ex.compile_expr(None, a, schema) for a in cd]).next()
+        cols = [got.column(i).to_pylist() for i in range(got.num_columns)]
+        keys = cols[0] if group else [0]
+        vals = cols[1:] if group else cols
+        assert {k: [vals[0][i], vals[1][i], vals[2][i]] for i, k in enumerate(keys)} == {k: [len(e[0]), len(e[1]), e[2]] for k, e in want.items()}, f"COUNT_DISTINCT group={bool(group)} nulls={nulls}"
+
+
+# ---- large inputs ------------------------------------------------------------------------------------------------------------------
+def dictionary_column(n, seed):
+    rng = np.random.default_rng(seed)
+    r = random.Random(seed)
+    names = sorted({"".join(r.choice("abcdefghijklmnopqrstuvwxyz é") for _ in range(r.randrange(4, 20))).strip() or "x" for _ in range(1000)})
+    codes = rng.integers(0, len(names), n, dtype=np.int32)
+    col = pa.array(names, pa.string()).take(pa.array(codes))
+    return names, codes, col
+
+
+def big_case(n, op, literal, batch_rows):
+    names, codes, col = dictionary_column(n, 11)
+    per_name = np.array([sterm(op, literal, s) for s in names], dtype=bool)
+    mask = per_name[codes]
+    schema = pa.schema([pa.field("s", pa.string(), False), pa.field("code", pa.int32(), False)])
+    full = pa.RecordBatch.from_arrays([col, pa.array(codes)], schema=schema)
+    batches = [full.slice(a, min(batch_rows, n - a)) for a in range(0, n, batch_rows)]
+    rel = ex.FilterRelation(ex.DataSourceRelation(schema, batches), ex.compile_scalar_expr(None, B(Column(0), op, utf8(literal)), schema), schema)
+    rel.keep_mask()
+    at = 0
+    for b in batches:
+        got = rel.next()
+        bits, rows = rel.last_mask(b.num_rows)
+        m = mask[at:at + b.num_rows]
+        assert rows == b.num_rows and np.array_equal(bits, np.packbits(m, bitorder="little")), f"bitmap of rows {at}.."
+        assert got.num_rows == int(m.sum())
+        assert np.array_equal(got.column(1).to_numpy(), codes[at:at + b.num_rows][m])
+        assert got.column(0).equals(b.column(0).filter(pa.array(m)))
+        at += b.num_rows
+    assert rel.next() is None
+    return mask.mean()
+
+
+def test_a_million_rows_and_three():
+    n = (1 << 20) + 3
+    for op, literal in ((Operator.Eq, None), (Operator.Lt, "m"), (Operator.Like, "%é%"), (Operator.NotLike, "a%"), (Operator.Like, "%a_b%")):
+        if literal is None:
+            literal = dictionary_column(8, 11)[0][500]
+        big_case(n, op, literal, n)
+
+
+def test_sixteen_million_rows_selective_and_dense():
+    n = 1 << 24
+    names = dictionary_column(8, 11)[0]  # sorted, about a thousand
+    assert 900 < len(names) <= 1000
+    lo = big_case(n, Operator.Lt, names[10], 1 << 23)      # the ten names that sort first: one row in a hundred
+    hi = big_case(n, Operator.GtEq, names[100], 1 << 23)   # nine names in ten
+    assert 0.005 < lo < 0.02 and 0.85 < hi < 0.95, (lo, hi)
