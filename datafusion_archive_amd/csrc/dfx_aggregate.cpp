@@ -950,6 +950,7 @@ Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now) {
 Status AggregateRelation::Impl::flush_pass2() {
   if (pt_pending == 0) return Status::OK();
   ++counters().agg_pass2_launches;
+  if (pt_pending > 1) ++counters().agg_deferred_windows;
   DFX_HIP(launch_partition_agg(T, PT, spill, 0, ctx().stream));
   pt_pending = 0;
   pt_fill_bound = 0;
@@ -1016,6 +1017,7 @@ Status AggregateRelation::Impl::handle_ctrl(const uint32_t* hc, int64_t n) {
     DFX_RETURN_IF_ERROR(flush_pass2());
     narrow = false;
     pt_layout_valid = false;
+    ++counters().agg_narrow_to_wide;
   }
   occupied_known = hc[CTRL_OCCUPIED];
   const uint64_t spilled = ((uint64_t)hc[CTRL_SPILL_HI] << 32) | hc[CTRL_SPILL_LO];
@@ -1058,6 +1060,7 @@ Status AggregateRelation::Impl::handle_ctrl(const uint32_t* hc, int64_t n) {
         DFX_HIP(hipMemcpyAsync(ctrl.get(), after, sizeof(uint32_t) * CTRL_WORDS, hipMemcpyHostToDevice, s));
         DFX_HIP(hipStreamSynchronize(s));  // `after` is a stack buffer
         occupied_known = after[CTRL_OCCUPIED];
+        ++counters().agg_replays_in_place;
         return Status::OK();
       }
       replay_from = spilled_now;
@@ -1210,6 +1213,7 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
     if (pt.flags & PTF_SHARED) ++counters().agg_shared_operand_launches;
     if (pt.flags & PTF_PAIR) ++counters().agg_pair_launches;
     if (pt.flags & PTF_PLANES) ++counters().agg_plane_launches;
+    if (pt.flags & PTF_HOT) ++counters().agg_hot_key_launches;
     ++pt_pending;
     pt_fill_bound += pt_worst;
     pt_rows_in_flight += n;
@@ -1231,6 +1235,7 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
   if (lds_enabled && lds_calibrated && !calibrating && opt().strategy != 1 && opt().fewgroup &&
       occupied_known > 0 && occupied_known <= 8 && fewgroup_supported(prog, fp, T)) {
     DFX_HIP(launch_fewgroup_agg(prog, fp, cols, p, T, spill, n, bytes, s));
+    ++counters().agg_fewgroup_launches;
     return Status::OK();
   }
   if (lds_enabled && opt().strategy != 1) {
@@ -1304,6 +1309,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
       std::swap(plan, plan_np);
       std::swap(fast, fast_np);
       unfused_now = true;
+      ++counters().agg_unfused_batches;
       const bool stop = stop_after_decision;  // (the filtered batch is this call's own: it is consumed whole, whatever is decided on the way)
       stop_after_decision = false;
       Status st = consume_batch_chunk(fb);
@@ -1401,6 +1407,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
     mostly_seen = ((remembered >> 60) & 1) != 0;
     remembered &= ~(15ull << 60);
     occupied_known = remembered;
+    ++counters().agg_memo_decisions;
     lds_calibrated = true;
     lds_enabled = remembered <= 8192;
     if (!lds_enabled && kw == 1 && remembered >= 16384) {
@@ -1412,6 +1419,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
     // calibration slice: measure the LDS front-cache hit rate and the group count on the first
     // 2^18 rows before committing the rest of the stream to a strategy
     const int64_t n0 = 1 << 18;
+    ++counters().agg_calibrations;
     calibrating = true;
     Status cst = launch_rows(b, prog, cols, 0, n0);
     calibrating = false;
@@ -1426,6 +1434,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b) {
       // slots: nothing replayed them first -- the spill cursor went on counting them, the rebuild after the batch replayed whatever
       // the new list's memory held in their place (60-80 of 200 000 groups missing, or keys that never were in the data).  Grow /
       // replay now; the decision then reads the real group count of the slice.
+      ++counters().agg_calibration_replays;
       DFX_RETURN_IF_ERROR(handle_ctrl(hc, n0));
       DFX_RETURN_IF_ERROR(read_ctrl(hc));
       if (hc[CTRL_ERROR]) return error_from_ctrl(hc[CTRL_ERROR]);
@@ -1647,6 +1656,7 @@ Status AggregateRelation::Impl::pair_fall_back() {
     DFX_RETURN_IF_ERROR(handle_ctrl(hc, 0));
   }
   ++counters().agg_pair_fallbacks;
+  if (flushed) ++counters().agg_pair_fallbacks_pending;
   pair_mode = false;
   install_chunks(std::move(single_chunks));
   single_chunks.clear();
@@ -1660,6 +1670,7 @@ Status AggregateRelation::Impl::run_held() {
   if (held.empty()) return Status::OK();
   std::vector<DeviceBatch> hb;
   hb.swap(held);
+  ++counters().agg_held_runs;
   held_bytes = 0;
   const int64_t seen = rows_seen;
   int64_t total = 0;

@@ -137,6 +137,18 @@ struct Counters {
   long long agg_pair_launches = 0;    // pass-1 launches that routed two operands per row (PTF_PAIR)
   long long agg_pair_fallbacks = 0;   // streams that left the pair scan for one scan per aggregate (the table outgrew the pair kernels' partitions, a batch the plan cannot bind)
   long long agg_growths = 0;
+  // transitions of the grouped aggregate's strategy state machine (tests/test_gpu_agg_state_machine.py): they observe, they decide nothing
+  long long agg_calibrations = 0;         // calibration slices run (first 2^18 rows of a first batch of more than 2^21)
+  long long agg_memo_decisions = 0;       // ... strategy decisions taken from a resident table's memo instead
+  long long agg_calibration_replays = 0;  // calibration slices that overflowed the table: grown / replayed before the decision
+  long long agg_replays_in_place = 0;     // spill lists replayed into the table as it was (no growth)
+  long long agg_narrow_to_wide = 0;       // streams that left the 12-byte routed rows: a key without a 32-bit image after a narrow decision
+  long long agg_fewgroup_launches = 0;    // launches of the register-accumulator kernel (<= 8 groups known)
+  long long agg_hot_key_launches = 0;     // pass-1 launches that kept heavy keys in LDS (PTF_HOT)
+  long long agg_unfused_batches = 0;      // batches filtered for real because of nulls under the absorbed predicate
+  long long agg_held_runs = 0;            // run_held(): every chunk over the held batches
+  long long agg_pair_fallbacks_pending = 0;  // agg_pair_fallbacks that found a deferred window still to aggregate
+  long long agg_deferred_windows = 0;     // pass-2 launches over more than one pass-1 launch
   // dfx_aggregate_exchange, per rank (bench.py --gpus N: extra.phases_ms): where a multi-GPU step's wall time goes
   long long xchg_calls = 0;
   long long xchg_local_us = 0;       // the rank's own scan + local aggregation (drain), until its stream is idle

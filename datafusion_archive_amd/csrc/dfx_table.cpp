@@ -469,6 +469,17 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_pair_fallbacks")) return counters().agg_pair_fallbacks;
   if (!strcmp(name, "agg_growths")) return counters().agg_growths;
   if (!strcmp(name, "agg_shared_operand_launches")) return counters().agg_shared_operand_launches;
+  if (!strcmp(name, "agg_calibrations")) return counters().agg_calibrations;
+  if (!strcmp(name, "agg_memo_decisions")) return counters().agg_memo_decisions;
+  if (!strcmp(name, "agg_calibration_replays")) return counters().agg_calibration_replays;
+  if (!strcmp(name, "agg_replays_in_place")) return counters().agg_replays_in_place;
+  if (!strcmp(name, "agg_narrow_to_wide")) return counters().agg_narrow_to_wide;
+  if (!strcmp(name, "agg_fewgroup_launches")) return counters().agg_fewgroup_launches;
+  if (!strcmp(name, "agg_hot_key_launches")) return counters().agg_hot_key_launches;
+  if (!strcmp(name, "agg_unfused_batches")) return counters().agg_unfused_batches;
+  if (!strcmp(name, "agg_held_runs")) return counters().agg_held_runs;
+  if (!strcmp(name, "agg_pair_fallbacks_pending")) return counters().agg_pair_fallbacks_pending;
+  if (!strcmp(name, "agg_deferred_windows")) return counters().agg_deferred_windows;
   if (!strcmp(name, "distinct_set_growths")) return counters().distinct_set_growths;
   if (!strcmp(name, "distinct_spill_rows")) return counters().distinct_spill_rows;
   if (!strcmp(name, "distinct_inserted")) return counters().distinct_inserted;

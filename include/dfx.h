@@ -467,7 +467,24 @@ int64_t dfx_relation_explain(struct ArrowArrayStream* stream, char* buf, size_t 
 int32_t dfx_set_option(const char* key, int64_t value);
 /* Measurement counters: "h2d_bytes" (column bytes the uploaders copied host -> device), "h2d_staged_bytes" (of which through
  * the pinned staging ring), "csv_cells" (cells the CSV source converted) -- what projection push-down saves, "csv_tiles" / "csv_general_tiles"
- * (64-record tiles converted by the CSV source / those that took the per-lane walk instead of the wave-cooperative path).  -1: unknown name. */
+ * (64-record tiles converted by the CSV source / those that took the per-lane walk instead of the wave-cooperative path).  -1: unknown name.
+ * Transitions of the grouped aggregate's strategy state machine (they observe only; tests/test_gpu_agg_state_machine.py asserts that
+ * its streams reach every one of them):
+ *   "agg_calibrations"            calibration slices run (first 2^18 rows of a first batch of more than 2^21 rows)
+ *   "agg_memo_decisions"          strategy decisions taken from a resident table's memo instead of a slice
+ *   "agg_calibration_replays"     slices that overflowed the table: grown / replayed before the decision read the group count
+ *   "agg_growths"                 tables rebuilt larger (rehash + replay of the spill list)
+ *   "agg_replays_in_place"        spill lists replayed into the table as it was (overflowing routing regions, no growth)
+ *   "agg_narrow_to_wide"          streams that left the 12-byte routed rows: a key without a 32-bit image after a narrow decision
+ *   "agg_pair_launches", "agg_plane_launches", "agg_shared_operand_launches"   pass-1 launches of the pair / plane / shared rows
+ *   "agg_pair_fallbacks"          streams that left the pair scan (or the planes) for one scan per aggregate ...
+ *   "agg_pair_fallbacks_pending"  ... of which with a deferred window still to aggregate
+ *   "agg_pass2_launches", "agg_deferred_windows"   pass-2 launches / those over more than one pass-1 launch
+ *   "agg_held_runs"               runs of every chunk of accumulators over the held batches (agg.chunk_hold)
+ *   "agg_fewgroup_launches"       launches of the register-accumulator kernel (at most 8 groups known)
+ *   "agg_hot_key_launches"        pass-1 launches that kept heavy keys in LDS
+ *   "agg_unfused_batches"         batches filtered for real because of nulls under the absorbed predicate
+ *   "distinct_set_growths", "distinct_spill_rows"  COUNT(DISTINCT) sets rehashed into larger ones / rows replayed from their spill lists */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 

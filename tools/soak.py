@@ -12,6 +12,9 @@ EXACT data distribution (every partial sum is representable, so any order of add
   random aggregate set (SUM / COUNT / MIN / MAX / AVG of v, of a second column w, of v * c) and predicate shape (two-sided,
   one-sided, three terms, none)        == under the defaults                            (every group, every aggregate, bit for bit)
 
+This soak compares the device with the device on purpose; the oracle-bound counterpart for the grouped aggregate's strategy decisions
+and their transitions is tests/test_gpu_agg_state_machine.py.
+
 usage: soak.py [seconds] [seed] [first iteration]    exit code 1 on the first violation or error (prints the case that failed)"""
 import os
 import sys
