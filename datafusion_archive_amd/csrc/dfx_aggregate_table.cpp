@@ -1,0 +1,583 @@
+// dfx_aggregate_table.cpp -- AggregateRelation: the table, its spill list and routing regions, the launches of one slice of rows,
+// the control-block pipeline that checks them one batch behind, growth and replay.
+#include "dfx_aggregate_impl.hpp"
+
+namespace dfx {
+
+// ---- table management ------------------------------------------------------------------------------
+Status AggregateRelation::Impl::alloc_table(int cap_log2, DevTable* Tn, std::vector<std::shared_ptr<void>>* owners,
+                                            bool new_ctrl, uint64_t** full_accs_out) {
+  hipStream_t s = ctx().stream;
+  memset(Tn, 0, sizeof(*Tn));
+  const uint64_t cap = 1ull << cap_log2;
+  Tn->stride = cap + 64;
+  Tn->mask = cap - 1;
+  Tn->shift = 64 - cap_log2;
+  Tn->kw = kw;
+  Tn->load_limit = cap / 2;
+  Tn->max_probe = (int)std::min<uint64_t>(cap, 1u << 30);
+  {  // probing block = what one workgroup can hold in 128 KB of LDS (keys + the accumulators of the widest chunk)
+    int widest = 1;
+    for (const Chunk& ch : chunks) widest = std::max(widest, ch.n);
+    if (phase != Phase::NotApplicable) widest = 1;  // (the partitioned strategy will run one accumulator per scan: blocks of 8192 slots, 256 partitions)
+    uint64_t blk = 16384 / (uint64_t)(std::max(kw, 1) + widest);  // 128 KB of LDS per block (pass 2: one workgroup per CU)
+    uint64_t p2 = 64;
+    while (p2 * 2 <= blk) p2 *= 2;
+    if (p2 > cap) p2 = cap;
+    Tn->block_mask = (uint32_t)(p2 - 1);
+  }
+  set_algebra(Tn);
+  Status st;
+  auto keys = device_alloc(sizeof(uint64_t) * Tn->stride * (size_t)std::max(kw, 1), &st);
+  if (!keys) return st;
+  auto accs = device_alloc(sizeof(uint64_t) * Tn->stride * (size_t)std::max(na_total, 1), &st);  // every chunk's planes
+  if (!accs) return st;
+  Tn->keys = (uint64_t*)keys.get();
+  Tn->accs = (uint64_t*)accs.get();
+  owners->clear();
+  owners->push_back(keys);
+  owners->push_back(accs);
+  if (kw > 1) {
+    auto slot_state = device_alloc(sizeof(uint32_t) * Tn->stride, &st);
+    if (!slot_state) return st;
+    Tn->state = (uint32_t*)slot_state.get();
+    owners->push_back(slot_state);
+    DFX_HIP(hipMemsetAsync(Tn->state, 0, sizeof(uint32_t) * Tn->stride, s));
+  } else {
+    DFX_HIP(launch_fill_u64(Tn->keys, kEmptyKey, (int64_t)Tn->stride, s));
+  }
+  for (int a = 0; a < na_total; ++a) DFX_HIP(launch_fill_u64(Tn->accs + (size_t)a * Tn->stride, acc_init_all[a], (int64_t)Tn->stride, s));
+  if (full_accs_out) *full_accs_out = Tn->accs;
+  Tn->accs += (uint64_t)chunks[(size_t)cur_chunk].a0 * Tn->stride;  // the caller gets the ACTIVE chunk's view
+  if (new_ctrl) {
+    ctrl = device_alloc(sizeof(uint32_t) * CTRL_WORDS, &st);
+    if (!ctrl) return st;
+    DFX_HIP(hipMemsetAsync(ctrl.get(), 0, sizeof(uint32_t) * CTRL_WORDS, s));
+    stats = device_alloc(sizeof(uint64_t) * kStatStripes * STAT_WORDS, &st);
+    if (!stats) return st;
+    DFX_HIP(hipMemsetAsync(stats.get(), 0, sizeof(uint64_t) * kStatStripes * STAT_WORDS, s));
+  }
+  Tn->ctrl = (uint32_t*)ctrl.get();
+  Tn->stats = (uint64_t*)stats.get();
+  return Status::OK();
+}
+
+Status AggregateRelation::Impl::ensure_spill(int64_t rows) {
+  if (rows <= 0) {
+    return Status::OK();
+  }
+  if (spill.words && spill.capacity >= (uint64_t)rows) return Status::OK();
+  DFX_RETURN_IF_ERROR(settle_ctrl());  // rows spilled by batches still in flight live in the old list
+  ScopedUs t_alloc(&counters().agg_alloc_us);
+  Status st;
+  int widest = na();  // the list is shared by every chunk of accumulators: planes for the widest one
+  for (const Chunk& ch : chunks) widest = std::max(widest, ch.n);
+  spill_owner = device_alloc(sizeof(uint64_t) * (size_t)rows * (size_t)(kw + widest), &st);
+  if (!spill_owner) return st;
+  spill.words = (uint64_t*)spill_owner.get();
+  spill.capacity = (uint64_t)rows;
+  return Status::OK();
+}
+
+// scratch for the partitioned strategy, sized for a batch of `rows` rows (worst case: all pass)
+// the active chunk's 2..3 aggregates all take the same operand (AVG's SUM and COUNT, SUM + MIN + MAX of one column ...):
+// with narrow keys and no nulls in this batch, routed rows carry that one operand (PTF_SHARED)
+bool AggregateRelation::Impl::shared_operand() const {
+  if (kw != 1 || na() < 2 || na() > 3 || !opt().shared_operand) return false;
+  for (int a = 1; a < na(); ++a)
+    if (active().plan.arg[a] != active().plan.arg[0]) return false;
+  return true;
+}
+
+Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now) {
+  const uint64_t S = (uint64_t)T.block_mask + 1;
+  const bool raw_ok = !nulls_now || (has_pred && !unfused_now);  // (a raw operand has no validity: fine under an absorbed predicate -- every surviving slot is valid)
+  const bool want_planes = pair_planes() && dec.narrow && opt().narrow_keys != 0 && raw_ok && same_operand_all() && kNarrowLine && opt().narrow_chunk16 &&
+                           opt().pass1_ws > 0 && opt().partition_layout != 2 && ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
+                           partition_ws_bytes((uint32_t)((T.mask + 1) / S), 4, 1) <= (size_t)158 * 1024;
+  const bool want_shared = !pair_scan() && dec.narrow && opt().narrow_keys != 0 && !nulls_now && shared_operand() &&
+                           ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
+                           partition_ring_bytes(2, (uint32_t)((T.mask + 1) / S), 16, false, true, 128) <= (size_t)158 * 1024;
+  const bool want_pair = pair_scan() && !split_is_shared && !want_shared && dec.narrow && kw == 1 && na() >= 2 && split_distinct == 2 && (na() == 2 || raw_ok) && kNarrowLine && opt().narrow_keys != 0 && opt().narrow_chunk16 &&
+                         opt().pass1_ws > 0 && opt().partition_layout != 2 && ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
+                         partition_ws_bytes((uint32_t)((T.mask + 1) / S), 8, 2) <= (size_t)158 * 1024;
+  if (pair_scan() && !want_pair && !want_planes)  // (a table block holds ONE accumulator plane in this mode: no other routed form fits; until the
+    return Status::Err(DFX_NOT_IMPLEMENTED, "pair scan: not for this table");  // next batch boundary the rows go through the global table)
+  const bool want_narrow = dec.narrow && kw == 1 && (na() == 1 || want_shared || want_pair || want_planes) && opt().narrow_keys != 0;
+  const uint32_t n_words = (want_shared || want_planes) ? 2u : (uint32_t)(kw + na());
+  if (win.layout_valid && rows <= win.layout_rows && PT.n_parts == (uint32_t)((T.mask + 1) / S) && PT.n_words == n_words &&
+      ((PT.flags & PTF_NARROW) != 0) == want_narrow && ((PT.flags & PTF_SHARED) != 0) == (want_shared || want_planes) && ((PT.flags & PTF_PAIR) != 0) == want_pair &&
+      ((PT.flags & PTF_PLANES) != 0) == (want_planes || (want_pair && na() > 2)))
+    return Status::OK();  // same table, a batch the regions were sized for: keep appending
+  DFX_RETURN_IF_ERROR(flush_pass2());  // rows routed under the old layout
+  win.layout_valid = false;
+  memset(&PT, 0, sizeof(PT));
+  PT.n_parts = (uint32_t)((T.mask + 1) / S);
+  PT.n_words = n_words;
+  int ps = 0;
+  while ((1ull << ps) < S) ++ps;
+  PT.part_shift = (uint32_t)ps;
+  if (PT.n_parts > 4096) return Status::Err(DFX_NOT_IMPLEMENTED, "partitioned strategy: too many table blocks");
+  // pass-1 flavour (agg.partition_mode).  Scattered 16-byte stores are transaction-bound at ~87 G rows/s on
+  // MI355X while runs of >= 64 bytes reach > 400 G rows/s (tools/ubench2.hip), so routed rows are write-combined
+  // in LDS whenever the partition count allows it:
+  //   2 (default)  lock-free per-partition LDS rings, 128-byte chunks, no barrier in the scan loop
+  //   1            workgroup-wide LDS counting sort (also for partition counts whose rings do not fit LDS)
+  //   0            one 16-byte store per row straight from registers (very many partitions)
+  const AggOptions& o = opt();
+  const uint32_t block = o.partition_block == 512 ? 512u : 1024u;
+  const size_t budget = block == 512 ? (size_t)79 * 1024 : (size_t)156 * 1024;
+  const uint32_t sort_cap = partition_sort_capacity(PT.n_words, PT.n_parts, block, budget);
+  const int want = o.partition_mode & 15;
+  if (want_shared) {
+    PT.flags |= PTF_NARROW | PTF_SHARED;
+    PT.mode = 2u;
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
+  } else if (want_planes) {
+    PT.flags |= PTF_NARROW | PTF_CHUNK16 | PTF_WS | PTF_SHARED | PTF_PLANES;
+    PT.ws_scanners = (o.pass1_ws == 4 || (dec.mostly_seen && o.pass1_ws_dense_scanners == 4)) ? 4u : 8u;  // (as for one aggregate)
+    PT.mode = 2u;
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
+  } else if (want_pair) {
+    PT.flags |= PTF_NARROW | PTF_CHUNK16 | PTF_WS | PTF_PAIR;
+    if (na() > 2) PT.flags |= PTF_PLANES;  // raw operands, a transform per accumulator in pass 2
+    PT.pair_ops = split_ops;
+    PT.pair_arg1 = split_arg1;
+    PT.ws_scanners = 8u;
+    PT.mode = 2u;
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
+  } else if (want == 2 && partition_ring_bytes(PT.n_words, PT.n_parts, 16) <= (size_t)158 * 1024) {
+    const bool hot = o.hot_keys > 0 || (o.hot_keys < 0 && dec.skew_seen);
+    const bool chunks8 = !((uint32_t)o.partition_mode & 0x80u);
+    if (want_narrow && chunks8) PT.flags |= PTF_NARROW;
+    if (hot && na() == 1 && chunks8 && partition_ring_bytes(PT.n_words, PT.n_parts, 16, true, (PT.flags & PTF_NARROW) != 0) <= (size_t)158 * 1024)
+      PT.flags |= PTF_HOT;
+    if ((PT.flags & PTF_NARROW) && !(PT.flags & PTF_HOT) && o.narrow_chunk16 && !(kNarrowLine && o.partition_layout == 2) /* LINE chunks: contiguous regions */ &&
+        partition_ring_bytes(PT.n_words, PT.n_parts, kNarrowRingRows, false, true) <= (size_t)158 * 1024)
+      PT.flags |= PTF_CHUNK16;
+    // selective scans: the scanning and the routing belong to different waves (dfx_k_partition_ws_inl.hpp).  When most rows
+    // pass, every wave has rows to route all the time and the ring kernel's symmetric waves are the better fit
+    // (round 5, 2^26-row launches, us per launch: ring kernel / 8 + 8 waves / 4 + 12 waves -- selectivity 0.2: - / 415 / 535; 0.5: 326 /
+    // 261 / 292; 0.8: 403 / 371 / 353; every row routed: 434 / 438 / 417-424 -- profiles/r05_pass1_ws_by_selectivity.txt.  So: always
+    // the wave-specialised kernel, four scanners once more than two thirds of the rows are routed.  agg.pass1_ws_dense = -1: never
+    // above one half, round 4's rule)
+    const bool ws_fits = o.pass1_ws_dense >= 0 || !dec.dense_seen;
+    if ((PT.flags & PTF_CHUNK16) && o.pass1_ws > 0 && ws_fits && !(((uint32_t)o.partition_mode) & ~15u)) {
+      // the split: 8 scanners + 8 routers; dense scans (more than half of the rows routed): 4 + 12 (agg.pass1_ws_dense_scanners)
+      PT.ws_scanners = (o.pass1_ws == 4 || (dec.mostly_seen && o.pass1_ws_dense_scanners == 4)) ? 4u : 8u;  // (agg.pass1_ws = 4: that split whatever the selectivity -- tests)
+      if (partition_ws_bytes(PT.n_parts, (int)PT.ws_scanners) <= (size_t)158 * 1024) PT.flags |= PTF_WS;
+    }
+    PT.mode = 2u | ((uint32_t)o.partition_mode & ~15u);
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
+  } else if (want == 2 && partition_ring_bytes(PT.n_words, PT.n_parts, 8) <= (size_t)158 * 1024) {
+    // several aggregates: rows of 3+ words.  8-row rings (two 4-row chunks) still fit where 16-row ones do not
+    PT.mode = 2u | 0x100u;
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
+  } else if (want != 0 && PT.n_parts <= 1024 && sort_cap >= 4 * PT.n_parts) {
+    PT.mode = 1u | ((uint32_t)o.partition_mode & ~15u);
+    PT.block = block;
+    PT.stage_rows = sort_cap;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count() * (int)(1024 / block));
+  } else {
+    // one producer workgroup (1024 lanes) per CU: producers x partitions x 128 B of open region lines
+    PT.mode = 0;
+    PT.block = 1024;
+    PT.stage_rows = 0;
+    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
+  }
+  const uint64_t avg = (uint64_t)rows / ((uint64_t)PT.n_producers * PT.n_parts) + 1;
+  // capacities are whole 64-row trips; LINE chunks (ten rows per 128-byte line, PTF_CHUNK16): whole lines as well
+  const uint64_t capq = (PT.flags & PTF_PAIR) ? (uint64_t)kPairCapQuantum : ((PT.flags & PTF_CHUNK16) && kNarrowLine) ? (uint64_t)kNarrowCapQuantum : 64ull;
+  win.worst = (uint32_t)((2 * avg + 64 + capq - 1) / capq * capq);
+  // regions hold `window` worst-case batches.  Deferral pays when few rows are routed (headline, 20 %: 2 batches per
+  // pass 2 = -3 % per query); when most rows are, the twice-as-long regions cost pass 1 more than the saved launches
+  // give back (config 3, 1e9 rows: 11.05 ms at 2, 10.08 ms at 1)
+  int window = o.partition_defer > 0 ? std::min(o.partition_defer, 16) : (int)std::max<int64_t>(1, std::min<int64_t>(8, ((int64_t)1 << 27) / std::max<int64_t>(rows, 1)));
+  if (dec.dense_seen) window = 1;
+  PT.cap_rows = win.worst * (uint32_t)window;
+  if (o.partition_cap_rows > 0) {  // tests: tiny regions (overflow -> spill list); no deferral
+    PT.cap_rows = (uint32_t)(((uint64_t)o.partition_cap_rows + capq - 1) / capq * capq);
+    win.worst = PT.cap_rows;
+  }
+  if (o.pass2_stream && na() == 1 && kw == 1) PT.flags |= PTF_STREAM_PASS2;
+  uint64_t pad_words = (uint64_t)(o.partition_pad >= 0 ? o.partition_pad : 0) / 8;
+  if ((PT.flags & PTF_CHUNK16) && kNarrowLine) pad_words = (pad_words + 15) / 16 * 16;  // (every region starts on a 128-byte line)
+  size_t row_bytes;
+  const bool line_chunks = (PT.flags & PTF_CHUNK16) && kNarrowLine;  // a region is cap_rows / 10 lines of 128 bytes
+  const bool pair_rows = (PT.flags & PTF_PAIR) != 0;  // ... cap_rows / 6 lines
+  const uint64_t region_words = pair_rows ? (uint64_t)(PT.cap_rows / (uint32_t)kPairChunkRows) * 16u
+                                : line_chunks ? (uint64_t)(PT.cap_rows / (uint32_t)kNarrowChunkRows) * (kNarrowSlotBytes / 8)
+                                : (PT.flags & PTF_NARROW) ? (uint64_t)PT.cap_rows * 12 / 8 : (uint64_t)PT.cap_rows * PT.n_words;
+  // one pass-2 trip's worth (64 contiguous rows, or six LINE chunks = 60 rows: 768 bytes either way): regions are contiguous (layouts 0 and 1)
+  PT.win_stride = pair_rows ? (uint64_t)(kPairTripBytes / 8u) : line_chunks ? 96u : region_words / (PT.cap_rows / 64);
+  if (o.partition_layout == 2) {  // windowed: window w of every partition of a producer side by side
+    PT.part_stride = PT.win_stride;
+    PT.win_stride = (uint64_t)PT.n_parts * PT.part_stride;
+    PT.prod_stride = (uint64_t)(PT.cap_rows / 64) * PT.win_stride + pad_words;
+    row_bytes = sizeof(uint64_t) * (size_t)PT.n_producers * PT.prod_stride;
+  } else if (o.partition_layout == 0) {  // partition-major (round 1)
+    PT.prod_stride = region_words;
+    PT.part_stride = (uint64_t)PT.n_producers * PT.prod_stride + pad_words;
+    row_bytes = sizeof(uint64_t) * (size_t)PT.n_parts * PT.part_stride;
+  } else {  // producer-major
+    PT.part_stride = region_words;
+    PT.prod_stride = (uint64_t)PT.n_parts * PT.part_stride + pad_words;
+    row_bytes = sizeof(uint64_t) * (size_t)PT.n_producers * PT.prod_stride;
+  }
+  const size_t cnt_bytes = sizeof(uint32_t) * (size_t)PT.n_parts * PT.n_producers;
+  Status st;
+  ScopedUs t_alloc(&counters().agg_alloc_us);
+  if (!win.rows || win.rows_bytes < row_bytes) {
+    win.rows.reset();
+    win.rows = device_alloc(row_bytes, &st);
+    if (!win.rows) return st;
+    win.rows_bytes = row_bytes;
+  }
+  if (!win.counts || win.cnt_bytes < cnt_bytes) {
+    win.counts.reset();
+    win.counts = device_alloc(cnt_bytes, &st);
+    if (!win.counts) return st;
+    win.cnt_bytes = cnt_bytes;
+  }
+  PT.rows = (uint64_t*)win.rows.get();
+  PT.counts = (uint32_t*)win.counts.get();
+  win.layout_valid = true;
+  win.layout_rows = rows;
+  win.closed();
+  return Status::OK();
+}
+
+// pass 2 over everything the pending pass-1 launches routed (no-op when nothing is pending)
+Status AggregateRelation::Impl::flush_pass2() {
+  if (win.pending == 0) return Status::OK();
+  ++counters().agg_pass2_launches;
+  if (win.pending > 1) ++counters().agg_deferred_windows;
+  DFX_HIP(launch_partition_agg(T, PT, spill, 0, ctx().stream));
+  win.closed();
+  win.last_p2_seq = ctl.batch_seq;
+  return Status::OK();
+}
+
+Status AggregateRelation::Impl::read_ctrl(uint32_t* host_ctrl) {
+  ScopedUs t(&counters().agg_sync_us);
+  hipStream_t s = ctx().stream;
+  DFX_HIP(hipMemcpyAsync(host_ctrl, ctrl.get(), sizeof(uint32_t) * CTRL_WORDS, hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));
+  return Status::OK();
+}
+
+// queue an asynchronous snapshot of the control block after the batch just launched.  The copy runs on the side
+// stream behind an event, so the next batch's kernels follow this batch's directly (an in-stream D2H copy costs
+// ~10 us of idle device per batch: rocprofv3 timeline).  The snapshot may already contain counts of the NEXT batch;
+// every word is monotone (errors, occupancy, spill cursor), so that only makes the check earlier.
+Status AggregateRelation::Impl::alloc_ctrl_host() {
+  Status st;
+  ctl.host = pinned_alloc(sizeof(uint32_t) * CTRL_WORDS * 2, &st);
+  if (!ctl.host) return st;
+  for (int i = 0; i < 2; ++i) {
+    DFX_HIP(hipEventCreateWithFlags(&ctl.ev[i], hipEventDisableTiming));
+    DFX_HIP(hipEventCreateWithFlags(&ctl.main_ev[i], hipEventDisableTiming));
+  }
+  return Status::OK();
+}
+
+Status AggregateRelation::Impl::post_ctrl(int64_t rows) {
+  hipStream_t s = ctx().stream;
+  hipStream_t aux = ctx().aux;
+  if (!ctl.host) DFX_RETURN_IF_ERROR(alloc_ctrl_host());
+  const int slot = (int)(ctl.batch_seq & 1);
+  if (win.snap_armed) {
+    // the batch's last kernel writes the snapshot into this slot of the pinned buffer: all there is to wait for is the
+    // kernel itself.  (The previous occupant of the slot, two batches back, was examined after the previous launch.)
+    win.snap_armed = false;
+    DFX_HIP(hipEventRecord(ctl.ev[slot], s));
+  } else {
+    if (ctl.pending[slot]) DFX_RETURN_IF_ERROR(examine_ctrl(slot));
+    DFX_HIP(hipEventRecord(ctl.main_ev[slot], s));
+    DFX_HIP(hipStreamWaitEvent(aux, ctl.main_ev[slot], 0));
+    DFX_HIP(hipMemcpyAsync((uint32_t*)ctl.host.get() + slot * CTRL_WORDS, ctrl.get(), sizeof(uint32_t) * CTRL_WORDS,
+                           hipMemcpyDeviceToHost, aux));
+    DFX_HIP(hipEventRecord(ctl.ev[slot], aux));
+  }
+  ctl.pending[slot] = true;
+  ctl.rows[slot] = rows;
+  ctl.seq[slot] = ctl.batch_seq;
+  ctl.unconfirmed_rows += (uint64_t)rows;
+  ++ctl.batch_seq;
+  return Status::OK();
+}
+
+// errors, growth: what the per-batch check has always done, on a (possibly one batch old) snapshot
+Status AggregateRelation::Impl::handle_ctrl(const uint32_t* hc, int64_t n) {
+  if (hc[CTRL_ERROR]) return error_from_ctrl(hc[CTRL_ERROR]);
+  if (dec.narrow && hc[CTRL_WIDE_KEYS] && pair_scan()) pair_wide_seen = true;  // (no wide form fits a block that holds one plane: consume_batch falls back)
+  if (dec.narrow && hc[CTRL_WIDE_KEYS] && !pair_scan()) {
+    // a key without a 32-bit image turned up (it went to the spill list): 16-byte rows from now on
+    DFX_RETURN_IF_ERROR(flush_pass2());
+    dec.narrow = false;
+    win.layout_valid = false;
+    ++counters().agg_narrow_to_wide;
+  }
+  dec.occupied_known = hc[CTRL_OCCUPIED];
+  const uint64_t spilled = ((uint64_t)hc[CTRL_SPILL_HI] << 32) | hc[CTRL_SPILL_LO];
+  uint64_t passed_total = 0;
+  if (getenv("DFX_DEBUG") && stats) {  // statistics stripes (debug only: one more synchronous copy)
+    std::vector<uint64_t> hs((size_t)kStatStripes * STAT_WORDS);
+    (void)hipMemcpy(hs.data(), stats.get(), sizeof(uint64_t) * hs.size(), hipMemcpyDeviceToHost);
+    for (int i = 0; i < kStatStripes; ++i) passed_total += hs[(size_t)i * STAT_WORDS + STAT_PASSED];
+  }
+  if (getenv("DFX_DEBUG"))
+    fprintf(stderr, "[dfx] batch n=%lld partition=%d lds=%d occupied=%u spilled=%llu saturated=%u passed=%llu cap=%llu "
+            "parts=%u cap_rows=%u stage=%u spillcap=%llu\n", (long long)n, (int)dec.use_partition, (int)dec.lds_enabled,
+            hc[CTRL_OCCUPIED], (unsigned long long)spilled, hc[CTRL_SATURATED],
+            (unsigned long long)passed_total,
+            (unsigned long long)(T.mask + 1), PT.n_parts, PT.cap_rows, PT.stage_rows, (unsigned long long)spill.capacity);
+  if (spilled > 0 || hc[CTRL_SATURATED] || dec.occupied_known > T.load_limit) {
+    // later batches may already be running against the saturated table: let them finish, then rebuild.  Rows still
+    // waiting in the routing regions belong to the blocks of THIS table: aggregate them first.
+    DFX_RETURN_IF_ERROR(flush_pass2());
+    uint32_t now[CTRL_WORDS];
+    DFX_RETURN_IF_ERROR(read_ctrl(now));
+    ctl.forget();
+    if (now[CTRL_ERROR]) return error_from_ctrl(now[CTRL_ERROR]);
+    uint64_t spilled_now = ((uint64_t)now[CTRL_SPILL_HI] << 32) | now[CTRL_SPILL_LO];
+    uint64_t replay_from = 0;
+    if (opt().replay_in_place && spilled_now > 0 && !now[CTRL_SATURATED] && now[CTRL_OCCUPIED] <= T.load_limit &&
+        2 * spilled_now <= spill.capacity) {
+      // The table is not full: the rows were spilled by overflowing routing regions (a hot key).  Put them into the
+      // table as it is; a row it cannot take is appended to the list BEHIND the rows being replayed (the cursor is not
+      // reset), and only those make the table grow.
+      hipStream_t s = ctx().stream;
+      DFX_HIP(launch_merge_rows(spill, 0, (int64_t)spilled_now, T, spill, s));
+      uint32_t after[CTRL_WORDS];
+      DFX_RETURN_IF_ERROR(read_ctrl(after));
+      if (after[CTRL_ERROR]) return error_from_ctrl(after[CTRL_ERROR]);
+      const uint64_t cursor = ((uint64_t)after[CTRL_SPILL_HI] << 32) | after[CTRL_SPILL_LO];
+      if (cursor == spilled_now && !after[CTRL_SATURATED] && after[CTRL_OCCUPIED] <= T.load_limit) {
+        after[CTRL_SPILL_LO] = after[CTRL_SPILL_HI] = 0;
+        DFX_HIP(hipMemcpyAsync(ctrl.get(), after, sizeof(uint32_t) * CTRL_WORDS, hipMemcpyHostToDevice, s));
+        DFX_HIP(hipStreamSynchronize(s));  // `after` is a stack buffer
+        dec.occupied_known = after[CTRL_OCCUPIED];
+        ++counters().agg_replays_in_place;
+        return Status::OK();
+      }
+      replay_from = spilled_now;
+      spilled_now = cursor;
+      memcpy(now, after, sizeof(now));
+    }
+    DFX_RETURN_IF_ERROR(grow_and_replay(now[CTRL_OCCUPIED], spilled_now, replay_from));
+    DFX_RETURN_IF_ERROR(read_ctrl(now));
+    dec.occupied_known = now[CTRL_OCCUPIED];
+  }
+  return Status::OK();
+}
+
+Status AggregateRelation::Impl::examine_ctrl(int slot) {
+  if (!ctl.pending[slot]) return Status::OK();
+  {
+    ScopedUs t(&counters().agg_ctrl_wait_us);
+    DFX_HIP(hipEventSynchronize(ctl.ev[slot]));
+  }
+  ctl.pending[slot] = false;
+  ctl.unconfirmed_rows -= std::min<uint64_t>(ctl.unconfirmed_rows, (uint64_t)ctl.rows[slot]);
+  uint32_t hc[CTRL_WORDS];
+  memcpy(hc, (const uint32_t*)ctl.host.get() + slot * CTRL_WORDS, sizeof(hc));
+  if (dec.use_partition && ctl.seq[slot] > win.last_p2_seq) {
+    // the snapshot was taken after the launch with sequence number ctrl_seq[slot] (it may already show later launches:
+    // only larger); every launch since then adds at most pt_worst rows to a region
+    const uint64_t later = (uint64_t)std::max<int64_t>(0, ctl.batch_seq - 1 - ctl.seq[slot]);
+    win.fill_bound = std::min<uint64_t>(win.fill_bound, (uint64_t)hc[CTRL_MAX_FILL] + later * win.worst);
+  }
+  return handle_ctrl(hc, ctl.rows[slot]);
+}
+
+// everything launched so far has been checked (end of input, or before the spill list is replaced)
+Status AggregateRelation::Impl::settle_ctrl() {
+  if (!ctl.pending[0] && !ctl.pending[1]) return Status::OK();
+  const int older = (int)(ctl.batch_seq & 1);  // the slot the NEXT batch would use holds the older snapshot
+  DFX_RETURN_IF_ERROR(examine_ctrl(older));
+  DFX_RETURN_IF_ERROR(examine_ctrl(older ^ 1));
+  return Status::OK();
+}
+
+// The table passed its load limit (or a probe sequence was exhausted): build a table at least 4x
+// larger, rehash, then replay the spilled rows into it.  Afterwards occupancy <= 1/4.
+Status AggregateRelation::Impl::grow_and_replay(uint64_t occupied, uint64_t spilled, uint64_t replay_from) {
+  ++counters().agg_growths;
+  hipStream_t s = ctx().stream;
+  if (spilled > spill.capacity)
+    return Status::Err(DFX_INTERNAL_ERROR, strfmt("group spill list overflow (%llu rows > capacity %llu)",
+                                                  (unsigned long long)spilled, (unsigned long long)spill.capacity));
+  const int cur_log2 = 64 - T.shift;
+  const int need_log2 = ceil_log2(4 * (occupied + (spilled - replay_from) + 1));
+  const int new_log2 = std::max(cur_log2 + 2, need_log2);
+  if (new_log2 > 31) return Status::Err(DFX_EXECUTION_ERROR, "GROUP BY table would exceed 2^31 slots");
+  DevTable Tn;
+  std::vector<std::shared_ptr<void>> owners;
+  uint64_t* accs_full_new = nullptr;
+  DFX_RETURN_IF_ERROR(alloc_table(new_log2, &Tn, &owners, false, &accs_full_new));
+  // reset the shared control words that describe the (new) table
+  uint32_t host_ctrl[CTRL_WORDS];
+  DFX_RETURN_IF_ERROR(read_ctrl(host_ctrl));
+  host_ctrl[CTRL_OCCUPIED] = 0;
+  host_ctrl[CTRL_SPILL_LO] = host_ctrl[CTRL_SPILL_HI] = 0;
+  host_ctrl[CTRL_SENTINEL] = 0;
+  host_ctrl[CTRL_SATURATED] = 0;  // (rehash re-raises the sentinel word when it meets the sentinel slot)
+  const DevRows no_spill = no_spill_rows();
+  // `from` still needs the old CTRL_SENTINEL to know whether slot `cap` is occupied: give the old
+  // table a private copy of the control block for the duration of the rehash
+  Status st;
+  auto old_ctrl = device_alloc(sizeof(uint32_t) * CTRL_WORDS, &st);
+  if (!old_ctrl) return st;
+  DFX_HIP(hipMemcpyAsync(old_ctrl.get(), ctrl.get(), sizeof(uint32_t) * CTRL_WORDS, hipMemcpyDeviceToDevice, s));
+  DFX_HIP(hipMemcpyAsync(ctrl.get(), host_ctrl, sizeof(uint32_t) * CTRL_WORDS, hipMemcpyHostToDevice, s));
+  DFX_HIP(hipStreamSynchronize(s));  // host_ctrl is a stack buffer
+  win.layout_valid = false;  // the routing regions are per table block
+  DevTable Told = T;
+  Told.ctrl = (uint32_t*)old_ctrl.get();
+  DFX_HIP(launch_rehash(Told, Tn, no_spill, s));
+  for (int c = 0; c < (int)chunks.size(); ++c) {  // the other chunks' planes move the same way (their keys are already in place)
+    if (c == cur_chunk) continue;
+    DFX_HIP(launch_rehash(view_of(Told, accs_full, c), view_of(Tn, accs_full_new, c), no_spill, s));
+  }
+  if (spilled > replay_from) DFX_HIP(launch_merge_rows(spill, (int64_t)replay_from, (int64_t)(spilled - replay_from), Tn, no_spill, s));
+  replace_table(Tn, accs_full_new, owners, false);  // old buffers return to the pool once the stream has passed them
+  DFX_HIP(hipStreamSynchronize(s));
+  return Status::OK();
+}
+
+// The table is replaced (growth, import).  A key column copied ahead of time (agg.early_keys) was made from the OLD table's slot
+// order and its side-stream kernels may still read the old planes: drop the copy (its buffers stay alive until they have run) and
+// make any later validity check fail.  forget_snapshot: also forget the previous snapshot's group count, so that the next copy waits
+// for two equal counts of the new table (the in-library exchange asks for it; growth and partial_import never did).
+void AggregateRelation::Impl::replace_table(const DevTable& Tn, uint64_t* accs_full_new, const std::vector<std::shared_ptr<void>>& owners, bool forget_snapshot) {
+  early.cancel();
+  ++table_generation;
+  if (forget_snapshot) early_last_occupied = ~0ull;
+  T = Tn;
+  accs_full = accs_full_new;
+  table_owners = owners;
+}
+
+// everything launched so far is aggregated and checked: the pending pass 2, the snapshots in flight and -- read_back -- the
+// control block as it is now (what ran after the last snapshot: errors, spilled rows, growth)
+Status AggregateRelation::Impl::finish_launched(int64_t rows, bool read_back) {
+  DFX_RETURN_IF_ERROR(flush_pass2());
+  DFX_RETURN_IF_ERROR(settle_ctrl());
+  if (!read_back) return Status::OK();
+  uint32_t hc[CTRL_WORDS];
+  DFX_RETURN_IF_ERROR(read_ctrl(hc));
+  return handle_ctrl(hc, rows);
+}
+
+Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgram& prog_in, const DevColumns& cols_in,
+                                            int64_t row0, int64_t n) {
+  hipStream_t s = ctx().stream;
+  win.snap_armed = false;
+  DevProgram prog = prog_in;
+  DevColumns cols = cols_in;
+  double bytes = 0;
+  for (int i = 0; i < prog.n_cols; ++i) {  // advance the bound columns to row0 (row0 is a multiple of 64)
+    const int w = prog.col_dtype[i] == T_BOOL ? 0 : dtype_width(prog.col_dtype[i]);
+    if (w) cols.c[i].values = (const uint8_t*)cols.c[i].values + (size_t)row0 * w;
+    else cols.c[i].bit_offset += row0;
+    if (cols.c[i].validity && w) cols.c[i].bit_offset += row0;
+    bytes += (double)n * (w ? w : 0.125);
+  }
+  DevAggPlan p = active().plan;
+  bool partition_now = dec.use_partition && partition_allowed();
+  if (partition_now) {
+    Status pst = ensure_partition(launch_rows_hint > 0 ? std::max<int64_t>(n, std::min<int64_t>(launch_rows_hint, b.num_rows)) : std::max<int64_t>(n, b.num_rows), prog.has_nulls != 0);  // (the slice after the calibration rows: size for the whole batch)
+    if (!pst.ok() && pst.code == DFX_NOT_IMPLEMENTED) partition_now = false;  // global-atomic path instead
+    else if (!pst.ok()) return pst;
+  }
+  if (partition_now) {
+    const DevFastPlan fpp = fast_plan();
+    DevPartition pt = PT;
+    if (win.pending > 0) pt.flags |= PTF_RESUME;
+    // close the window when one more batch could overflow a region (or the batch budget is used up; the calibration
+    // slice is aggregated at once: the strategy decision reads the group count)
+    const int max_batches = pair_scan() ? std::min(2, std::max(1, opt().partition_defer_batches)) : std::max(1, opt().partition_defer_batches);  // (pair scan: the spill list's sizing)
+    const bool close_window = calibrating || win.pending + 1 >= max_batches || win.fill_bound + 2 * (uint64_t)win.worst > PT.cap_rows;
+    // the LAST kernel of this batch publishes the control block itself (examined one batch later, see post_ctrl)
+    win.snap_armed = false;
+    uint32_t* snap_to = nullptr;
+    if (opt().ctrl_snapshot == 1 && dec.calibrated && !calibrating) {
+      if (!ctl.host) DFX_RETURN_IF_ERROR(alloc_ctrl_host());
+      if (!win.snap_done) {
+        Status st;
+        win.snap_done = device_alloc(sizeof(uint32_t) * 16, &st);
+        if (!win.snap_done) return st;
+        DFX_HIP(hipMemsetAsync(win.snap_done.get(), 0, sizeof(uint32_t) * 16, s));
+      }
+      snap_to = (uint32_t*)ctl.host.get() + (size_t)(ctl.batch_seq & 1) * CTRL_WORDS;
+      win.snap_armed = true;
+    }
+    if (!close_window) {
+      pt.snap_host = snap_to;
+      pt.snap_done = (uint32_t*)win.snap_done.get();
+    }
+    DFX_HIP(launch_partition(prog, fpp, cols, p, T, pt, spill, n, bytes, s));
+    if (pt.flags & PTF_SHARED) ++counters().agg_shared_operand_launches;
+    if (pt.flags & PTF_PAIR) ++counters().agg_pair_launches;
+    if (pt.flags & PTF_PLANES) ++counters().agg_plane_launches;
+    if (pt.flags & PTF_HOT) ++counters().agg_hot_key_launches;
+    ++win.pending;
+    win.fill_bound += win.worst;
+    win.rows_in_flight += n;
+    if (close_window) {
+      PT.snap_host = snap_to;
+      PT.snap_done = (uint32_t*)win.snap_done.get();
+      Status fst = flush_pass2();
+      PT.snap_host = nullptr;
+      PT.snap_done = nullptr;
+      DFX_RETURN_IF_ERROR(fst);
+    }
+    return Status::OK();
+  }
+  const DevFastPlan fp = fast_plan();
+  // a handful of groups (the calibration slice / earlier batches saw <= 8): register accumulators.  Should more
+  // groups turn up later the kernel still handles them (through the table), and the next batch goes back to K7.
+  if (dec.lds_enabled && dec.calibrated && !calibrating && opt().strategy != 1 && opt().fewgroup &&
+      dec.occupied_known > 0 && dec.occupied_known <= 8 && fewgroup_supported(prog, fp, T)) {
+    DFX_HIP(launch_fewgroup_agg(prog, fp, cols, p, T, spill, n, bytes, s));
+    ++counters().agg_fewgroup_launches;
+    return Status::OK();
+  }
+  if (dec.lds_enabled && opt().strategy != 1) {
+    const AggOptions& o = opt();
+    int slots = o.lds_slots >= 0 ? o.lds_slots : 4096;
+    if (calibrating && o.lds_slots < 0) slots = 512;  // calibration slice: the cache only has to tell few groups from many
+    while (slots > 64 && (size_t)slots * ((size_t)(kw + na()) * 8 + (kw > 1 ? 4 : 0)) > 64 * 1024) slots >>= 1;
+    int copies = o.lds_copies > 0 ? o.lds_copies : 1;
+    if (o.lds_copies <= 0 && dec.calibrated) {  // few groups: lane-replicated sub-tables
+      if (dec.occupied_known <= 16) copies = 16;
+      else if (dec.occupied_known <= 128) copies = 4;
+    }
+    while (copies > 1 && slots / copies < 64) copies >>= 1;
+    p.lds_slots = slots;
+    p.lds_copies = copies;
+  } else {
+    p.lds_slots = 0;
+    p.lds_copies = 1;
+  }
+  DFX_HIP(launch_hash_agg(prog, fp, cols, p, T, spill, n, bytes, s));
+  return Status::OK();
+}
+
+}  // namespace dfx
