@@ -582,16 +582,10 @@ int32_t dfx_aggregate_relation_new_with_options(const struct ArrowSchema* schema
   return c_abi_guard(err, errlen, [&]() -> int32_t {
     if (!out || (n_options > 0 && !options)) return to_c(Status::Err(DFX_GENERAL, "null argument"), err, errlen);
     OptionOverrides ov;
-    {
-      AggOptions probe = agg_options();
-      for (int i = 0; i < n_options; ++i) {
-        if (!options[i].key || !set_option_in(probe, options[i].key, options[i].value))
-          return to_c(Status::Err(DFX_GENERAL, std::string("unknown option ") + (options[i].key ? options[i].key : "(null)")), err, errlen);
-        ov.emplace_back(options[i].key, options[i].value);
-      }
-    }
+    Status st = parse_option_overrides(options, n_options, &ov);
+    if (!st.ok()) return to_c(st, err, errlen);
     std::unique_ptr<Relation> in;
-    Status st = adopt_input_stream(input, &in);
+    st = adopt_input_stream(input, &in);
     if (!st.ok()) return to_c(st, err, errlen);
     SchemaInfo si;
     st = schema_from_arrow(schema, &si);

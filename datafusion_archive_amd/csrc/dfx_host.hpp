@@ -3,7 +3,7 @@
 //
 // The internal operator tree mirrors the reference's: `struct Relation` below is
 // src/execution/relation.rs:27-32 with RecordBatch replaced by a device-resident batch.  The
-// Arrow C Stream adapters at the library edge (dfx_relation.cpp) convert to / from host Arrow.
+// Arrow C Stream adapters at the library edge (dfx_host_stream.cpp, dfx_export.cpp) convert to / from host Arrow.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

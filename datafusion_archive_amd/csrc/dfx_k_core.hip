@@ -1131,7 +1131,7 @@ hipError_t launch_filter_fused(const DevProgram& P, const DevFastPlan& fast, con
 }
 
 // mask &= other, per-tile counts of the result: a predicate too large for one fused program is evaluated as several
-// conjuncts (FilterRelation, dfx_relation.cpp); one wave per 64-word tile
+// conjuncts (FilterRelation, dfx_filter.cpp); one wave per 64-word tile
 __global__ __launch_bounds__(256) void k_mask_and_count(uint64_t* __restrict__ mask, const uint64_t* __restrict__ other,
                                                         uint32_t* __restrict__ tile_counts, const int64_t n_words,
                                                         const int64_t n_tiles) {

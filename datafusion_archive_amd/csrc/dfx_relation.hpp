@@ -12,7 +12,7 @@ struct dfx_comm;
 
 namespace dfx {
 
-// ---- stream adapters --------------------------------------------------------------------------
+// ---- stream adapters (dfx_host_stream.cpp, dfx_export.cpp) --------------------------------------
 // Takes ownership of *input (moves the struct). If the stream was produced by this library the
 // inner device relation is unwrapped, otherwise the host stream is wrapped in an uploader.
 Status adopt_input_stream(struct ArrowArrayStream* input, std::unique_ptr<Relation>* out);
@@ -20,6 +20,8 @@ Status adopt_input_stream(struct ArrowArrayStream* input, std::unique_ptr<Relati
 void export_relation(std::unique_ptr<Relation> rel, struct ArrowArrayStream* out);
 // The relation behind one of our exported streams (nullptr if foreign). Not owning.
 Relation* peek_exported(struct ArrowArrayStream* s);
+// The relation out of one of our exported streams, owning; the stream is consumed (nullptr, stream untouched, if foreign).
+std::unique_ptr<Relation> take_exported(struct ArrowArrayStream* s);
 
 // ---- table scan (dfx_table.cpp) -----------------------------------------------------------------
 struct TableData {
@@ -149,6 +151,20 @@ struct OperatorOptions {
   AggOptions opt_;
   bool frozen_ = false;
 };
+// the option list of a *_new_with_options call: every key must be one dfx_set_option knows
+Status parse_option_overrides(const dfx_option* options, int32_t n_options, OptionOverrides* overrides);
+
+// ---- shared by the operators (dfx_relation.cpp) ----------------------------------------------------
+// CTRL_ERROR bits -> the reference's error
+Status error_from_ctrl(uint32_t bits);
+// an operator's control block (CTRL_WORDS words), zeroed on the library's stream
+Status alloc_zeroed_ctrl(std::shared_ptr<void>* ctrl);
+// error bits the caller already has on the host: zeroes the block for the next batch, returns their error
+Status clear_ctrl_error(const std::shared_ptr<void>& ctrl, uint32_t bits, hipStream_t stream);
+// reads CTRL_ERROR back (pageable 4-byte copy, one synchronisation of `stream`); non-zero: clear_ctrl_error
+Status take_ctrl_error(const std::shared_ptr<void>& ctrl, hipStream_t stream);
+// bytes of `batch` that the program of `builder` reads over n rows (what the launchers report to the profiler)
+double program_input_bytes(const ProgramBuilder& builder, const DeviceBatch& batch, int64_t n);
 
 // ---- FilterRelation (src/execution/filter.rs) ---------------------------------------------------
 class FilterRelation : public Relation {
@@ -204,6 +220,29 @@ class FilterRelation : public Relation {
   };
   std::vector<Part> more_;
   Status build_parts();
+  // ---- next() and its steps (dfx_filter.cpp) ----
+  struct Bound {  // one fused program bound to a batch
+    DevProgram prog;
+    DevColumns cols;
+    DevFastPlan fast;
+    double in_bytes = 0;  // the bitmap it writes + the columns it reads
+  };
+  struct Batch {  // one non-empty input batch on its way through next()
+    int64_t n = 0, n_words = 0, n_tiles = 0;
+    std::shared_ptr<void> mask;                     // the bitmap that decides (a whole-predicate Utf8 term brings its own)
+    std::shared_ptr<void> counts, offsets, tmp;     // kept rows per tile, their exclusive scan (n_tiles + 1), the scan's scratch
+    uint64_t kept = 0;                              // read back from offsets[n_tiles] / the control block
+    std::vector<std::shared_ptr<void>> fused_vals;  // index into in.columns -> the column as the single-pass kernel compacted it
+  };
+  Status bind_program(const ProgramBuilder& builder, const DevFastPlan& fast, const DeviceBatch& pin, int64_t n, Bound* p);
+  Status alloc_scratch(const DeviceBatch& in, bool with_mask, Batch* b);
+  Status emit_empty(const DeviceBatch& in, DeviceBatch* out);
+  Status mask_from_term(const DeviceBatch& ext, Batch* b);
+  Status mask_single_pass(const DeviceBatch& in, const Bound& p, Batch* b, bool* done);  // *done false: the look-back stalled, take two passes
+  Status mask_two_pass(const DeviceBatch& pin, const Bound& first, Batch* b);
+  Status queue_scan_and_kept(Batch* b);
+  Status compact_fixed(const DeviceColumn& ic, size_t c, const Batch& b, DeviceColumn* oc);
+  Status compact_utf8(const DeviceColumn& ic, const Batch& b, DeviceColumn* oc);
 };
 
 // ---- ProjectRelation (src/execution/projection.rs) ----------------------------------------------
@@ -291,8 +330,6 @@ bool has_distinct_aggregate(const std::vector<dfx_runtime_expr>& aggr);
 Status make_distinct_aggregate(SchemaInfo schema, std::unique_ptr<Relation> input, std::vector<dfx_runtime_expr> group,
                                std::vector<dfx_runtime_expr> aggr, OptionOverrides options, std::unique_ptr<Relation>* out);
 
-// shared by filter / aggregate: CTRL_ERROR bits -> the reference's error
-Status error_from_ctrl(uint32_t bits);
 void set_exchange_test_failure(int64_t v);  // dfx_exchange.cpp: dfx_set_option("test.exchange_fail", rank << 8 | stage)
 
 }  // namespace dfx

@@ -1589,7 +1589,7 @@ def test_aggregate_over_a_table_scan_merges_small_scan_batches():
 @pytest.mark.parametrize("mode", ["in order (default)", "staged ring", "staged ring as the operator's own option", "one batch ahead", "one batch ahead + pinned in place"])
 def test_host_batches_are_borrowed_until_their_copy_has_finished(tmp_path, mode):
     """Row (g) of the round-2 review: the producer's release callback must fire only after the copy of ITS batch has read the
-    buffers -- in every form of the host stream (csrc/dfx_relation.cpp; option "host.stream"): in order (0, the default: copies
+    buffers -- in every form of the host stream (csrc/dfx_host_stream.cpp; option "host.stream"): in order (0, the default: copies
     on the library's stream, release after the synchronisation), the pinned staging ring (1, round 4: library threads copy the
     producer's buffers into pinned slots, the array is released when they have joined), one batch ahead on a copy stream
     (2: release on the copy's event) and with the producer's buffers page-locked in place on top of that (3).

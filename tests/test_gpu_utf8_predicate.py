@@ -314,6 +314,45 @@ def test_projection_push_down_and_explain():
     assert got.column(0).to_pylist() == [int(np.array(t["w"])[mask].sum())]
 
 
+def test_string_term_beside_a_conjunction_of_several_programs_under_a_projection():
+    """`s LIKE 'b%' AND c0 > .. AND c0 < .. AND ... c11 < ..`: the term's bitmap is a virtual Boolean column, and the AND chain (13
+    columns, 24 literals) does not fit one fused program -- every program of the split binds to the batch WITH the virtual
+    column, their masks are ANDed.  Under a projection that reads three columns (a Utf8 column the predicate never sees, a
+    predicate column as it is and one in a sum): only those are compacted.  4096 + 37 rows (one tile boundary, a ragged last
+    word) and a ragged second batch; the oracle runs `m = 1 AND ...` over the Python mask of the term.  Bit for bit."""
+    rng, prng = np.random.default_rng(41), random.Random(41)
+    n = 4096 + 37 + 700
+    s = [None if prng.random() < 0.1 else prng.choice(["alpha", "beta", "b", "bz", "c", "gamma", "délta", "be", ""]) for _ in range(n)]
+    arrays, names = [pa.array(s, pa.string()), pa.array([prng.choice(["x", "yé", "", "zzzz"]) for _ in range(n)], pa.string())], ["s", "u"]
+    chain = []
+    for c in range(12):
+        if c % 3 == 2:
+            vals, lo, hi = rng.integers(-1000, 1000, n).astype(np.int64), i64(-900), i64(950)
+        else:
+            vals, lo, hi = rng.integers(0, 1 << 20, n).astype(np.float64) / 1024.0, f64(8.0 + c), f64(1000.0 - c)
+        arrays.append(pa.array(vals, mask=(rng.random(n) < 0.03) if c % 4 == 1 else None))
+        names.append(f"c{c}")
+        chain += [B(Column(2 + c), Operator.Gt, lo), B(Column(2 + c), Operator.Lt, hi)]
+    full, m_is_1 = with_mask(pa.RecordBatch.from_arrays(arrays, names=names), term_mask(Operator.Like, "b%", s))
+    batches, schema = [full.slice(0, 4096 + 37), full.slice(4096 + 37)], full.schema
+
+    def conj(first):
+        for t in chain:
+            first = B(first, Operator.And, t)
+        return first
+
+    exprs = [Column(1), Column(2 + 3), B(Column(2 + 0), Operator.Plus, f64(1.0))]
+    rel = ex.FilterRelation(ex.DataSourceRelation(schema, batches), ex.compile_scalar_expr(None, conj(B(Column(0), Operator.Like, utf8("b%"))), schema), schema)
+    rel = ex.ProjectRelation(rel, [ex.compile_scalar_expr(None, e, schema) for e in exprs], None)
+    text = ex.explain(rel)
+    assert "fused programs (masks ANDed)" in text and "Utf8 string terms evaluated per batch" in text and ", 3 columns compacted" in text, text
+    got = list(rel)
+    want = [oracle.project_next(exprs, oracle.filter_next(conj(m_is_1), b)) for b in batches]
+    assert len(got) == 2 and 0 < want[0].num_rows < 4096
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert_batches_identical(g, w, f"term + split conjunction + projection, batch {i}")
+
+
 def test_resident_table_scanned_twice():
     t = mix_table(n=20000)
     _, batches, mask = run_typed(t, [], B(S, Operator.Lt, utf8("c")), lambda r: sterm(Operator.Lt, "c", r["s"]), "")
