@@ -594,7 +594,7 @@ int32_t dfx_aggregate_relation_new_with_options(const struct ArrowSchema* schema
     for (int i = 0; i < n_group; ++i) g.push_back(*group_exprs[i]);
     for (int i = 0; i < n_aggr; ++i) a.push_back(*aggr_exprs[i]);
     std::unique_ptr<Relation> rel;
-    if (has_distinct_aggregate(a)) {  // COUNT(DISTINCT): its own relation around a plain aggregate (dfx_distinct.cpp)
+    if (needs_distinct_sets(a, in->schema())) {  // COUNT(DISTINCT), MIN / MAX of Utf8: a relation of its own around a plain aggregate (dfx_distinct.cpp)
       st = make_distinct_aggregate(si, std::move(in), std::move(g), std::move(a), std::move(ov), &rel);
       if (!st.ok()) return to_c(st, err, errlen);
       export_relation(std::move(rel), out);

@@ -353,12 +353,8 @@ using namespace dfx;
 
 extern "C" {
 
-static const char kDistinctExchange[] =
-    "COUNT_DISTINCT: distinct counts do not add across ranks (the exchange of (key, value) tuples is not implemented)";
-static bool is_distinct_stream(struct ArrowArrayStream* s) {
-  Relation* r = peek_exported(s);
-  return r && r->kind() == REL_DISTINCT_AGGREGATE;
-}
+// a stream over distinct sets (COUNT_DISTINCT, MIN / MAX of Utf8) has no partial state to exchange
+static Status distinct_stream_refusal(struct ArrowArrayStream* s) { return distinct_sets_exchange_refusal(peek_exported(s)); }
 
 static AggregateRelation* as_aggregate(struct ArrowArrayStream* s) {
   Relation* r = peek_exported(s);
@@ -369,7 +365,7 @@ static AggregateRelation* as_aggregate(struct ArrowArrayStream* s) {
 int32_t dfx_aggregate_partial_build(struct ArrowArrayStream* agg, int32_t world, int32_t* n_words, int64_t* counts,
                                     char* err, size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
-    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
+    if (Status refused = distinct_stream_refusal(agg); !refused.ok()) return to_c(refused, err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     int nw = 0;
@@ -382,7 +378,7 @@ int32_t dfx_aggregate_partial_build(struct ArrowArrayStream* agg, int32_t world,
 int32_t dfx_aggregate_partial_export(struct ArrowArrayStream* agg, void* dst_device, int64_t dst_words, char* err,
                                      size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
-    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
+    if (Status refused = distinct_stream_refusal(agg); !refused.ok()) return to_c(refused, err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     return to_c(a->partial_export(dst_device, dst_words), err, errlen);
@@ -392,7 +388,7 @@ int32_t dfx_aggregate_partial_export(struct ArrowArrayStream* agg, void* dst_dev
 int32_t dfx_aggregate_partial_import(struct ArrowArrayStream* agg, const void* src_device, const int64_t* counts,
                                      int32_t n_buckets, char* err, size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
-    if (is_distinct_stream(agg)) return to_c(Status::Err(DFX_NOT_IMPLEMENTED, kDistinctExchange), err, errlen);
+    if (Status refused = distinct_stream_refusal(agg); !refused.ok()) return to_c(refused, err, errlen);
     AggregateRelation* a = as_aggregate(agg);
     if (!a) return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     return to_c(a->partial_import(src_device, counts, n_buckets), err, errlen);

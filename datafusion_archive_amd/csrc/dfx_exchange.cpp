@@ -622,8 +622,8 @@ void dfx_comm_destroy(dfx_comm* c) {
 int32_t dfx_aggregate_exchange(struct ArrowArrayStream* agg, dfx_comm* comm, int64_t* stats, char* err, size_t errlen) {
   return c_abi_guard(err, errlen, [&]() -> int32_t {
     Relation* r = peek_exported(agg);
-    if (r && r->kind() == REL_DISTINCT_AGGREGATE)  // (dfx_distinct.cpp: distinct counts do not add across ranks)
-      return to_c(Status::Err(DFX_NOT_IMPLEMENTED, "COUNT_DISTINCT: distinct counts do not add across ranks (the exchange of (key, value) tuples is not implemented)"), err, errlen);
+    if (Status refused = distinct_sets_exchange_refusal(r); !refused.ok())  // (dfx_distinct.cpp: COUNT_DISTINCT, MIN / MAX of Utf8)
+      return to_c(refused, err, errlen);
     if (!r || r->kind() != REL_AGGREGATE)
       return to_c(Status::Err(DFX_GENERAL, "not an aggregate stream of this library"), err, errlen);
     return to_c(static_cast<AggregateRelation*>(r)->exchange(comm, stats), err, errlen);

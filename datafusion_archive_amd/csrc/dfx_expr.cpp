@@ -22,6 +22,14 @@
 //       is always valid, the result never null): a null slot gives Eq false, NotEq true, Lt / LtEq true, Gt / GtEq false, and by analogy
 //       with Eq / NotEq Like false, NotLike true (recalled, unpinned).  A literal or pattern of more than 4096 bytes: NotImplemented at
 //       compile time.  Anything else with a Utf8 literal, Like on other operands, Utf8 column against Utf8 column: refused as before.
+//   D10 MIN / MAX of a Utf8 column (typed by the planner like any aggregate, sqlplanner.rs:309-322: the return type is the argument's;
+//       the executor panics on the downcast, aggregate.rs:561-603): the argument a bare Utf8 column, the result a nullable Utf8 column
+//       named like the aggregate.  Order is Rust `str` Ord, D9's (the empty string is a value and the smallest).  Null arguments are
+//       skipped, grouped and ungrouped; a group whose arguments are all null reports NULL, ungrouped over no non-null row one row holding
+//       NULL, grouped over empty input zero rows.  (Over a Filter no argument is null: fn filter's output is all-valid, filter.rs:83-92, so
+//       a null slot that passes the predicate is the value its bytes spell, the empty string for an Arrow-built null.)  Another declared return type: the InternalError of a numeric mismatch; more GROUP BY
+//       expressions than COUNT_DISTINCT takes: NotImplemented; both at creation (dfx_distinct.cpp folds the extrema from the distinct
+//       set of the argument at emit, dfx_k_utf8agg.hip).  Parity unpinned.
 #include <charconv>
 #include <string.h>
 #include <strings.h>

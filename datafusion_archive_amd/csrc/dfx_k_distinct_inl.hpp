@@ -125,31 +125,42 @@ __global__ __launch_bounds__(kBlock) void k_distinct_count(const DevTable S, con
 }
 
 
-// emitted group keys -> their distinct counts (0: the group has no counted tuple).  Cnt is complete and quiescent: plain loads.
+// The emit-time tables (the count table here, the extrema table of dfx_k_utf8agg.hip) are keyed by the key prefix: row i of the
+// emitted key columns as such a key, and its slot (table_upsert_slot's probe sequence).  The table is complete and quiescent:
+// plain loads.  KW > 1: the emit-time table of a grouped query is at least two words wide.
+template <int KW>
+DEV void distinct_prefix_key(const DevDistinctKeys& K, int kw_out, int64_t i, uint64_t (&key)[KW]) {
+#pragma unroll
+  for (int k = 0; k < KW; ++k) key[k] = k < kw_out ? load_canonical(K.dtype[k], K.values[k], i, 0) : 0ull;
+}
+template <int KW>
+DEV bool distinct_prefix_find(const DevTable& Cnt, const uint64_t (&key)[KW], uint64_t& slot_out) {
+  uint64_t slot = ((hash_keys<KW>(key) >> Cnt.shift) & Cnt.mask) & ~3ull;
+  for (int p = 0; p < Cnt.max_probe; ++p) {
+    const uint32_t st = Cnt.state[slot];
+    if (st == 0u) return false;
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) eq = eq && Cnt.keys[(uint64_t)k * Cnt.stride + slot] == key[k];
+    if (eq) {
+      slot_out = slot;
+      return true;
+    }
+    slot = (slot & ~(uint64_t)Cnt.block_mask) | ((slot + 1) & (uint64_t)Cnt.block_mask);
+  }
+  return false;
+}
+
+// emitted group keys -> their distinct counts (0: the group has no counted tuple)
 template <int KW>
 __global__ __launch_bounds__(kBlock) void k_distinct_lookup(const DevTable Cnt, const DevDistinctKeys K, const int kw_out,
                                                             const int64_t n, uint64_t* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     uint64_t key[KW];
-#pragma unroll
-    for (int k = 0; k < KW; ++k) key[k] = k < kw_out ? load_canonical(K.dtype[k], K.values[k], i, 0) : 0ull;
-    uint64_t c = 0;
-    if (KW > 1) {  // (the count table of a grouped query is at least two words wide)
-      uint64_t slot = ((hash_keys<KW>(key) >> Cnt.shift) & Cnt.mask) & ~3ull;  // table_upsert_slot's probe sequence
-      for (int p = 0; p < Cnt.max_probe; ++p) {
-        const uint32_t st = Cnt.state[slot];
-        if (st == 0u) break;
-        bool eq = true;
-#pragma unroll
-        for (int k = 0; k < KW; ++k) eq = eq && Cnt.keys[(uint64_t)k * Cnt.stride + slot] == key[k];
-        if (eq) {
-          c = Cnt.accs[slot];
-          break;
-        }
-        slot = (slot & ~(uint64_t)Cnt.block_mask) | ((slot + 1) & (uint64_t)Cnt.block_mask);
-      }
-    }
+    distinct_prefix_key<KW>(K, kw_out, i, key);
+    uint64_t c = 0, slot = 0;
+    if (KW > 1 && distinct_prefix_find<KW>(Cnt, key, slot)) c = Cnt.accs[slot];
     out[i] = c;
   }
 }

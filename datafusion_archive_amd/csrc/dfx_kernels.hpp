@@ -34,6 +34,7 @@ enum KernelId : int {
   KID_DISTINCT_INSERT,
   KID_DISTINCT_COUNT,
   KID_UTF8_PRED,
+  KID_UTF8_EXTREMA,
   KID_COUNT_
 };
 const char* kernel_name(int kid);
@@ -235,6 +236,15 @@ hipError_t launch_distinct_insert(const DevProgram& P, const DevFastPlan& fast, 
                                   const DevTable& T, const DevRows& spill, int64_t n, bool* plan_kernel, hipStream_t s);
 hipError_t launch_distinct_count(const DevTable& S, const DevTable& Cnt, uint64_t* total, hipStream_t s);
 hipError_t launch_distinct_lookup(const DevTable& Cnt, const DevDistinctKeys& K, int kw_out, int64_t n, uint64_t* out, hipStream_t s);
+
+// MIN / MAX of a Utf8 column (dfx_k_utf8agg.hip, deviation D10): folded at emit from the distinct set of (key words, padding,
+// dictionary id of the argument).  fold: every tuple of S into the extrema table Ex (the count table's twin: S.kw words, the
+// argument word zeroed, two zeroed planes min id + 1 / max id + 1; ungrouped, S.kw == 1: Ex.stride == 1, its one entry), strings
+// compared out of D (n_ids: the ids D holds); planes: bit 0 the minimum, bit 1 the maximum.  lookup: emitted group keys -> the ids
+// of plane `plane` (null_id where the group has none), the validity words ((n + 63) / 64) and *nulls += null rows.
+hipError_t launch_utf8_extrema_fold(const DevTable& S, const DevTable& Ex, const DevDict& D, uint64_t n_ids, uint32_t planes, hipStream_t s);
+hipError_t launch_utf8_extrema_lookup(const DevTable& Ex, const DevDistinctKeys& K, int kw_out, int64_t n, int plane, uint64_t null_id,
+                                      uint64_t* ids, uint64_t* validity, uint64_t* nulls, hipStream_t s);
 
 // synthetic columns (definition shared with oracle/dfx_oracle.c: orc_synth_fill)
 hipError_t launch_synth(int kind, int column_id, double p0, double p1, uint64_t seed, int64_t row_begin,

@@ -323,10 +323,13 @@ class AggregateRelation : public Relation {
   std::unique_ptr<Impl> impl_;
 };
 
-// ---- COUNT(DISTINCT) (dfx_distinct.cpp, deviation D8) -----------------------------------------------
-// An aggregate list with a COUNT_DISTINCT runs as a relation of its own (REL_DISTINCT_AGGREGATE) around a plain
-// AggregateRelation over the other aggregates.  Limits it cannot take are returned here, at creation.
-bool has_distinct_aggregate(const std::vector<dfx_runtime_expr>& aggr);
+// ---- aggregates over distinct sets (dfx_distinct.cpp: COUNT(DISTINCT), deviation D8; MIN / MAX of a Utf8 column, D10) ------
+// An aggregate list with a COUNT_DISTINCT, or a MIN / MAX whose argument is Utf8 (over input_schema), runs as a relation of its own
+// (REL_DISTINCT_AGGREGATE) around a plain AggregateRelation over the other aggregates.  Limits it cannot take are returned
+// by make_distinct_aggregate, at creation.
+bool needs_distinct_sets(const std::vector<dfx_runtime_expr>& aggr, const SchemaInfo& input_schema);
+// such a stream takes no part in the multi-GPU exchange: OK for any other relation, else DFX_NOT_IMPLEMENTED naming what reads its sets
+Status distinct_sets_exchange_refusal(const Relation* r);
 Status make_distinct_aggregate(SchemaInfo schema, std::unique_ptr<Relation> input, std::vector<dfx_runtime_expr> group,
                                std::vector<dfx_runtime_expr> aggr, OptionOverrides options, std::unique_ptr<Relation>* out);
 

@@ -190,6 +190,9 @@ int32_t dfx_synchronize(char* err, size_t errlen);
  * unsupported aggregate :103-106).
  * Aggregate names (matched case-insensitively): MIN, MAX, SUM, COUNT, AVG and COUNT_DISTINCT (one argument, return type
  * UInt64: the number of distinct non-null argument values; a Rust shim maps AggregateType::CountDistinct to this name).
+ * MIN / MAX also take a bare Utf8 Column with return type Utf8 (deviation D10: the planner types them so, sqlplanner.rs:309-322,
+ * the reference's executor panics): a nullable Utf8 result in Rust `str` ordering (the order of the string terms below; the empty
+ * string is the smallest), null arguments skipped, NULL for a group without a non-null argument.
  * Utf8 string terms (deviation D9): a BinaryExpr of a bare Utf8 Column and a Utf8 Literal compiles -- Eq NotEq Lt LtEq Gt GtEq
  * with the literal on either side, Like / NotLike with the column on the left and the pattern on the right -- to a Boolean
  * expression named by its Debug form (`#4 Eq Utf8("CO")`), alone or anywhere under AND / OR beside numeric terms.  Ordering is
@@ -233,9 +236,11 @@ int32_t dfx_project_relation_new(struct ArrowArrayStream* input, const dfx_runti
 
 /* replaces AggregateRelation::new(schema, input, group_expr, aggr_expr) + impl Relation
  * (src/execution/aggregate.rs:47-61, :614-631, :703-952).  `schema` may be NULL or empty
- * (context.rs:185 passes Schema::empty()).  With a COUNT_DISTINCT among the aggregates the stream is a distinct aggregate
- * around a plain one: more than 7 GROUP BY expressions are DFX_NOT_IMPLEMENTED here, and so are the partial / exchange
- * calls below on such a stream (distinct counts do not add across ranks). */
+ * (context.rs:185 passes Schema::empty()).  With a COUNT_DISTINCT or a MIN / MAX of a Utf8 column among the aggregates the
+ * stream is a distinct aggregate around a plain one (one distinct set per argument; the Utf8 extrema are folded from theirs at
+ * emit): more than 7 GROUP BY expressions are DFX_NOT_IMPLEMENTED here, a MIN / MAX of Utf8 declared with another return type is
+ * DFX_INTERNAL_ERROR here, and the partial / exchange calls below on such a stream are DFX_NOT_IMPLEMENTED (distinct counts do
+ * not add across ranks; the extrema's dictionary ids are rank-local). */
 int32_t dfx_aggregate_relation_new(const struct ArrowSchema* schema, struct ArrowArrayStream* input,
                                    const dfx_runtime_expr* const* group_exprs, int32_t n_group,
                                    const dfx_runtime_expr* const* aggr_exprs, int32_t n_aggr,
