@@ -118,6 +118,9 @@ struct Counters {
   long long filter_lookback_fallbacks = 0;  // ... batches redone in two passes because the look-back gave up waiting (a shared GPU)  // ... of which through the pinned staging ring (HostStreamOptions::mode 1)
   long long csv_cells = 0;  // cells converted by the CSV source
   long long csv_tiles = 0;          // 64-record tiles the CSV cell kernel converted ...
+  long long csv_write_cells = 0;          // cells the CSV writer formatted (dfx_csv_write.cpp) ...
+  long long csv_write_bytes = 0;          // ... bytes of text it wrote, the header included ...
+  long long csv_write_general_tiles = 0;  // ... 64-row tiles whose text did not fit the LDS window (a lane per row, the wave on a long string)
   long long csv_general_tiles = 0;  // ... of them through the per-lane walk (quotes, ragged records, a tile longer than the LDS window)
   // host-side time accounting of the aggregate (microseconds; tools/kprobe.py): where a query's wall time goes beyond its kernels
   long long agg_ctrl_wait_us = 0;   // blocked on control-block snapshots (one batch behind the launches)

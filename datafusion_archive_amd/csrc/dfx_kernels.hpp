@@ -35,6 +35,7 @@ enum KernelId : int {
   KID_DISTINCT_COUNT,
   KID_UTF8_PRED,
   KID_UTF8_EXTREMA,
+  KID_CSV_WRITE,
   KID_COUNT_
 };
 const char* kernel_name(int kid);

@@ -458,6 +458,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_early_keys_late")) return counters().agg_early_keys_late;
   if (!strcmp(name, "csv_tiles")) return counters().csv_tiles;
   if (!strcmp(name, "csv_general_tiles")) return counters().csv_general_tiles;
+  if (!strcmp(name, "csv_write_cells")) return counters().csv_write_cells;
+  if (!strcmp(name, "csv_write_bytes")) return counters().csv_write_bytes;
+  if (!strcmp(name, "csv_write_general_tiles")) return counters().csv_write_general_tiles;
   if (!strcmp(name, "agg_ctrl_wait_us")) return counters().agg_ctrl_wait_us;
   if (!strcmp(name, "agg_sync_us")) return counters().agg_sync_us;
   if (!strcmp(name, "agg_emit_us")) return counters().agg_emit_us;

@@ -299,6 +299,19 @@ class LimitRelation(Relation):
         self._keep = [input]
 
 
+def write_csv(relation: Relation, filename: str, options: Optional[dict] = None):
+    """The executor of PhysicalPlan::Write { plan, filename, kind: CSV } (physicalplan.rs:24-29; the reference has none):
+    consumes `relation` to its end and writes it to `filename` as CSV text formatted on the device (include/dfx.h:
+    dfx_csv_write has the format).  Returns (rows, bytes of the file).  `options`: none is defined, any key is refused."""
+    err = _errbuf()
+    opts, n_opts, _keep = _options(options)
+    rows, nbytes = ctypes.c_int64(), ctypes.c_int64()
+    code = _ffi.lib().dfx_csv_write(ctypes.byref(relation._take_stream()), os.fsencode(filename), opts, n_opts,
+                                    ctypes.byref(rows), ctypes.byref(nbytes), err, 1024)
+    _check(code, err)
+    return rows.value, nbytes.value
+
+
 class AggregateRelation(Relation):
     """aggregate::AggregateRelation::new(schema, input, group_expr, aggr_expr) (aggregate.rs:47-52)."""
 

@@ -336,6 +336,31 @@ int32_t dfx_csv_datasource_new(const char* filename, const struct ArrowSchema* s
                                struct ArrowArrayStream* out, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
+ * CSV writer.  The executor of PhysicalPlan::Write { plan, filename, kind } -- "execute a logical plan and write the output
+ * to a file" (src/execution/physicalplan.rs:24-29) -- which the reference declares and never runs; kind = CSV.  A sink: it
+ * consumes `input` to its end (a stream of this library stays on the device, a foreign stream is uploaded like any operator
+ * input), formats every batch as text on the device and writes `filename`.  rows_out / bytes_out (may be NULL): rows written,
+ * bytes of the file (header included).  Deviation D11, parity unpinned (arrow 0.12 has no csv writer); the contract is the
+ * library's own reader: the file read back by dfx_csv_datasource_new with the same schema gives the same rows bit for bit.
+ *   layout    one header record with the field names (the reader always consumes the first record), one record per row,
+ *             delimiter ',', terminator '\n' also after the last record
+ *   integers  plain decimal, '-' for negatives;  Boolean  true / false
+ *   floats    the shortest digits that parse back to the same bits IN THE COLUMN'S WIDTH (the closest such), laid out as Rust's
+ *             {:?}: positional with at least one digit after the point for 1e-4 <= |x| < 1e16 and zero (1.0 0.1 -0.0), else
+ *             d[.ddd]e[-]x (1e16 1.5e-5 5e-324); NaN, inf, -inf.  A Float64 cell is at most 24 bytes, a Float32 cell 19
+ *   Utf8      the bytes as they are, quoted iff the cell holds ',' '"' CR or LF, every '"' doubled inside quotes; header names alike
+ *   nulls     an empty cell;  a file of ONE column writes an empty cell as "" (the reader skips blank lines)
+ *   exceptions to the round trip: a null Utf8 slot comes back as the empty string (the reader never produces Utf8 nulls);
+ *             every NaN payload comes back as one NaN
+ * `options`: none is defined, any key is DFX_GENERAL.  Errors: a path that cannot be created or written is DFX_IO_ERROR, a
+ * column type outside Boolean .. Utf8 is DFX_NOT_IMPLEMENTED naming the type, no device is DFX_EXECUTION_ERROR (there is no
+ * host formatting path).  The text goes to `filename` + ".dfx-partial" and is renamed at the end: a failed call leaves
+ * nothing under the final name.
+ * ---------------------------------------------------------------------------------------- */
+int32_t dfx_csv_write(struct ArrowArrayStream* input, const char* filename, const dfx_option* options, int32_t n_options,
+                      int64_t* rows_out, int64_t* bytes_out, char* err, size_t errlen);
+
+/* ------------------------------------------------------------------------------------------
  * ORDER BY / LIMIT.  The operators behind LogicalPlan::Sort { expr: [Expr::Sort { expr, asc }], input, schema } and
  * LogicalPlan::Limit { limit, input, schema } (src/logicalplan.rs:313-338), which the reference's planner emits
  * (sqlplanner.rs:142-183) and its executor leaves at unimplemented!() (context.rs:113,194): there is no reference
@@ -418,6 +443,13 @@ int32_t dfx_debug_plan_term(int32_t dtype, int32_t op, uint64_t literal, uint64_
  * or DFX_OP_NOT_LIKE; literal: the NUL-terminated literal / pattern; value, value_len: the value's bytes; is_null: the value is
  * null.  Returns 0 / 1, or -1 for a bad call (another operator, a null pointer, a literal of more than 4096 bytes).  No GPU needed. */
 int32_t dfx_debug_utf8_term(int32_t op, const char* literal, const uint8_t* value, int64_t value_len, int32_t is_null);
+/* Debug: one value formatted as dfx_csv_write formats a cell, on the host, by the code the kernel runs per cell
+ * (csrc/dfx_numfmt.hpp); the twin of dfx_debug_utf8_term.  dtype DFX_BOOLEAN .. DFX_FLOAT64: `bits` is the value in its
+ * canonical 64-bit form (Float32 bits in the low word; wider bits of a narrow integer are ignored), the cell is written to
+ * buf.  dtype DFX_UTF8: buf holds the value's bytes on entry, `bits` is their number (bit 63 set: the file has one column,
+ * so an empty cell is written ""), and the cell replaces them.  Returns the cell's length (a NUL follows if there is room),
+ * or -1 for a bad call (another dtype, a null or too small buffer).  No GPU needed. */
+int32_t dfx_debug_format_value(int32_t dtype, uint64_t bits, char* buf, size_t buflen);
 /* Pulls every batch of a library stream and drops it on the device: no host RecordBatch, no D2H copy (what a stacked
  * operator would see).  rows / batches (may be NULL): what came out. */
 int32_t dfx_relation_drain_device(struct ArrowArrayStream* stream, int64_t* rows, int64_t* batches, char* err, size_t errlen);
@@ -473,6 +505,8 @@ int32_t dfx_set_option(const char* key, int64_t value);
 /* Measurement counters: "h2d_bytes" (column bytes the uploaders copied host -> device), "h2d_staged_bytes" (of which through
  * the pinned staging ring), "csv_cells" (cells the CSV source converted) -- what projection push-down saves, "csv_tiles" / "csv_general_tiles"
  * (64-record tiles converted by the CSV source / those that took the per-lane walk instead of the wave-cooperative path).  -1: unknown name.
+ * "csv_write_cells" / "csv_write_bytes" / "csv_write_general_tiles" (dfx_csv_write: cells formatted, bytes of text written, 64-row
+ * tiles whose text did not fit the LDS window and took the lane-per-row path).
  * Transitions of the grouped aggregate's strategy state machine (they observe only; tests/test_gpu_agg_state_machine.py asserts that
  * its streams reach every one of them):
  *   "agg_calibrations"            calibration slices run (first 2^18 rows of a first batch of more than 2^21 rows)

@@ -122,6 +122,8 @@ extern "C" {
                                                out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_csv_datasource_new(filename: *const c_char, schema: *const ArrowSchema, batch_size: i64,
                               out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
+    fn dfx_csv_write(input: *mut ArrowArrayStream, filename: *const c_char, options: *const DfxOption, n_options: i32,
+                     rows_out: *mut i64, bytes_out: *mut i64, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_sort_relation_new(input: *mut ArrowArrayStream, exprs: *const *const DfxRuntimeExpr, ascending: *const i32,
                              n: i32, schema: *const ArrowSchema, out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_limit_relation_new(input: *mut ArrowArrayStream, limit: i64, schema: *const ArrowSchema,
@@ -641,6 +643,16 @@ impl GpuRelation {
 }
 
 impl GpuRelation {
+    /// PhysicalPlan::Write { plan, filename, kind: CSV } (physicalplan.rs:24-29): consumes the relation to its end and writes
+    /// it as CSV text formatted on the device; returns (rows, bytes of the file).
+    pub fn write_csv(mut self, filename: &str) -> Result<(usize, usize)> {
+        let mut err = [0 as c_char; ERRLEN];
+        let name = CString::new(filename).unwrap();
+        let (mut rows, mut bytes) = (0i64, 0i64);
+        let code = unsafe { dfx_csv_write(&mut *self.stream, name.as_ptr(), ptr::null(), 0, &mut rows, &mut bytes, err.as_mut_ptr(), ERRLEN) };
+        check(code, &err)?;
+        Ok((rows as usize, bytes as usize))
+    }
     /// Physical plan of this operator and everything the library chained below it: what was fused, which kernel family
     /// runs each program (the counterpart of the `println!("Logical plan: ...")` in context.rs:105).
     pub fn explain(&mut self) -> String {
