@@ -32,7 +32,6 @@ Status AggregateRelation::Impl::setup(const SchemaInfo& input_schema) {
     d.key = (int)k;
     d.src_col = r.column;
     d.virt_col = (int)bind_schema.fields.size();
-    memset(&d.D, 0, sizeof(d.D));
     Field f;
     f.name = "__dict_ids_" + std::to_string(k);
     f.dtype = DFX_UINT64;
@@ -554,7 +553,7 @@ Status AggregateRelation::next(DeviceBatch* out, bool* has) {
     return Status::Err(DFX_INTERNAL_ERROR, "assertion failed: record batch needs at least one column");
   DFX_RETURN_IF_ERROR(m.drain());
   if (m.kw == 0) DFX_RETURN_IF_ERROR(m.emit_ungrouped(out));
-  // (Utf8 keys: dict_emit indexes the dictionary with the compacted ids before the scan's total could contradict the host's
+  // (Utf8 keys: Utf8Dict::to_utf8 indexes the dictionary with the compacted ids before the scan's total could contradict the host's
   // count -- the table's own count first, one round trip more)
   else DFX_RETURN_IF_ERROR(m.emit_grouped(out, (m.opt().emit_async && m.dicts.empty()) ? (int64_t)m.dec.occupied_known : -1));
   *has = true;

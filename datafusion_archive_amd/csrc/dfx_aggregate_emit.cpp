@@ -1,147 +1,7 @@
-// dfx_aggregate_emit.cpp -- AggregateRelation: the Utf8 key dictionary, the key column copied ahead of time, and the result batch.
+// dfx_aggregate_emit.cpp -- AggregateRelation: the key column copied ahead of time, and the result batch.
 #include "dfx_aggregate_impl.hpp"
 
 namespace dfx {
-
-// ---- Utf8 key dictionary (host side of dfx_k_dict.hip) ------------------------------------------------
-// (re)allocate a dictionary with 2^slots_log2 slots (ids capacity = half of that) and `pool_cap` pool bytes;
-// keep == true carries the strings of completed batches over and rebuilds the slot table from them
-Status AggregateRelation::Impl::dict_alloc(DictKey& d, int slots_log2, uint64_t pool_cap, bool keep) {
-  hipStream_t s = ctx().stream;
-  const uint64_t slots = 1ull << slots_log2, id_cap = slots / 2;
-  Status st;
-  auto dstate = device_alloc(sizeof(uint32_t) * slots, &st);
-  if (!dstate) return st;
-  auto hash = device_alloc(sizeof(uint64_t) * slots, &st);
-  if (!hash) return st;
-  auto sid = device_alloc(sizeof(uint64_t) * slots, &st);
-  if (!sid) return st;
-  auto str_off = device_alloc(sizeof(uint64_t) * id_cap, &st);
-  if (!str_off) return st;
-  auto str_len = device_alloc(sizeof(uint32_t) * id_cap, &st);
-  if (!str_len) return st;
-  auto pool = device_alloc(std::max<uint64_t>(pool_cap, 64), &st);
-  if (!pool) return st;
-  auto cursors = device_alloc(sizeof(uint64_t) * DICT_WORDS, &st);
-  if (!cursors) return st;
-  DFX_HIP(hipMemsetAsync(dstate.get(), 0, sizeof(uint32_t) * slots, s));
-  if (keep && d.allocated) {
-    if (d.pool_used) DFX_HIP(hipMemcpyAsync(pool.get(), d.pool.get(), d.pool_used, hipMemcpyDeviceToDevice, s));
-    if (d.ids_used) {
-      DFX_HIP(hipMemcpyAsync(str_off.get(), d.str_off.get(), sizeof(uint64_t) * d.ids_used, hipMemcpyDeviceToDevice, s));
-      DFX_HIP(hipMemcpyAsync(str_len.get(), d.str_len.get(), sizeof(uint32_t) * d.ids_used, hipMemcpyDeviceToDevice, s));
-    }
-  } else {
-    d.ids_used = d.pool_used = 0;
-  }
-  const uint64_t hc[DICT_WORDS] = {d.pool_used, d.ids_used, 0, 0};
-  DFX_HIP(hipMemcpyAsync(cursors.get(), hc, sizeof(hc), hipMemcpyHostToDevice, s));
-  DFX_HIP(hipStreamSynchronize(s));  // hc is a stack buffer; the old arrays are released below
-  d.state = dstate; d.hash = hash; d.sid = sid; d.str_off = str_off; d.str_len = str_len; d.pool = pool; d.cursors = cursors;
-  d.D.state = (uint32_t*)dstate.get();
-  d.D.hash = (uint64_t*)hash.get();
-  d.D.sid = (uint64_t*)sid.get();
-  d.D.str_off = (uint64_t*)str_off.get();
-  d.D.str_len = (uint32_t*)str_len.get();
-  d.D.pool = (uint8_t*)pool.get();
-  d.D.cursors = (uint64_t*)cursors.get();
-  d.D.mask = slots - 1;
-  d.D.shift = 64 - slots_log2;
-  d.D.id_cap = id_cap;
-  d.D.pool_cap = std::max<uint64_t>(pool_cap, 64);
-  d.allocated = true;
-  if (d.ids_used) DFX_HIP(launch_dict_rebuild(d.D, d.ids_used, s));
-  return Status::OK();
-}
-
-// ids of one batch's strings; grows the dictionary (ids stay stable) and re-encodes when it overflows
-Status AggregateRelation::Impl::dict_encode(DictKey& d, const DeviceColumn& src, int64_t n, DeviceColumn* ids_col) {
-  hipStream_t s = ctx().stream;
-  Status st;
-  auto ids = device_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(n, 1), &st);
-  if (!ids) return st;
-  if (!d.allocated) {
-    int lg = opt().dict_capacity_log2 > 0 ? opt().dict_capacity_log2 : 16;
-    lg = std::max(4, std::min(lg, 30));
-    DFX_RETURN_IF_ERROR(dict_alloc(d, lg, std::max<uint64_t>((uint64_t)src.data_bytes * 2, 1u << 16), false));
-  }
-  for (int attempt = 0; n > 0; ++attempt) {
-    if (attempt > 16) return Status::Err(DFX_INTERNAL_ERROR, "Utf8 key dictionary does not converge");
-    DFX_HIP(launch_dict_encode(src.offsets, src.data, n, d.D, d.ids_used, (uint64_t*)ids.get(), s));
-    uint64_t hc[DICT_WORDS];
-    DFX_HIP(hipMemcpyAsync(hc, d.D.cursors, sizeof(hc), hipMemcpyDeviceToHost, s));
-    DFX_HIP(hipStreamSynchronize(s));
-    if (hc[DICT_OVERFLOW] == 2) return Status::Err(DFX_INTERNAL_ERROR, "Utf8 key dictionary: slot claim timed out");
-    if (hc[DICT_OVERFLOW] == 0) {
-      d.ids_used = hc[DICT_IDS];
-      d.pool_used = hc[DICT_POOL];
-      break;
-    }
-    // overflow: forget this attempt (its ids were not used yet), grow x4 (slots / ids) and to fit the batch (pool)
-    int lg = 64 - d.D.shift;
-    const uint64_t want_ids = std::max<uint64_t>(hc[DICT_IDS], d.ids_used + 1);
-    while ((1ull << lg) / 2 < want_ids * 2 && lg < 31) ++lg;
-    lg = std::min(31, std::max(lg, 64 - d.D.shift + 2));
-    const uint64_t want_pool = std::max<uint64_t>(hc[DICT_POOL], d.pool_used + (uint64_t)src.data_bytes) * 2;
-    DFX_RETURN_IF_ERROR(dict_alloc(d, lg, std::max<uint64_t>(want_pool, d.D.pool_cap), true));
-  }
-  ids_col->dtype = DFX_UINT64;
-  ids_col->length = n;
-  ids_col->null_count = 0;
-  ids_col->values = ids.get();
-  ids_col->validity = nullptr;
-  ids_col->bit_offset = 0;
-  ids_col->owners.clear();
-  ids_col->owners.push_back(ids);
-  return Status::OK();
-}
-
-// group ids -> Arrow Utf8 column (offsets + data) on the device
-Status AggregateRelation::Impl::dict_emit(const DictKey& d, const uint64_t* ids, int64_t g, DeviceColumn* out) {
-  hipStream_t s = ctx().stream;
-  Status st;
-  auto lens = device_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(g, 1), &st);
-  if (!lens) return st;
-  auto starts = device_alloc(sizeof(uint64_t) * (size_t)(g + 1), &st);
-  if (!starts) return st;
-  auto tmp = device_alloc(sizeof(uint64_t) * (size_t)(g / 4096 + 4), &st);
-  if (!tmp) return st;
-  auto offs = device_alloc(sizeof(int32_t) * (size_t)(g + 1), &st);
-  if (!offs) return st;
-  uint64_t total = 0;
-  if (g > 0) {
-    DFX_HIP(launch_dict_lengths(ids, g, d.D, (uint32_t*)lens.get(), s));
-    DFX_HIP(launch_scan_u32((const uint32_t*)lens.get(), (uint64_t*)starts.get(), g, (uint64_t*)tmp.get(), s));
-    DFX_HIP(hipMemcpyAsync(&total, (uint64_t*)starts.get() + g, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    DFX_HIP(hipStreamSynchronize(s));
-  } else {
-    DFX_HIP(hipMemsetAsync(starts.get(), 0, sizeof(uint64_t), s));
-  }
-  if (total > 0x7FFFFFFFull) return Status::Err(DFX_EXECUTION_ERROR, "Utf8 group keys exceed 2 GB (Arrow Utf8 offsets are 32-bit)");
-  auto data = device_alloc((size_t)std::max<uint64_t>(total, 8), &st);
-  if (!data) return st;
-  DFX_HIP(launch_dict_gather(ids, g, d.D, (const uint64_t*)starts.get(), (int32_t*)offs.get(), (uint8_t*)data.get(), s));
-  out->dtype = DFX_UTF8;
-  out->length = g;
-  out->null_count = 0;
-  out->values = nullptr;
-  out->offsets = (const int32_t*)offs.get();
-  out->data = (const uint8_t*)data.get();
-  out->data_bytes = (int64_t)total;
-  out->owners.clear();
-  out->owners.push_back(offs);
-  out->owners.push_back(data);
-  return Status::OK();
-}
-
-// ---- output ------------------------------------------------------------------------------------------
-static Status upload_small(const void* host, size_t bytes, std::shared_ptr<void>* dev) {
-  Status st;
-  *dev = device_alloc(bytes ? bytes : 8, &st);
-  if (!*dev) return st;
-  if (bytes) DFX_HIP(hipMemcpy(dev->get(), host, bytes, hipMemcpyHostToDevice));
-  return Status::OK();
-}
 
 Status AggregateRelation::Impl::emit_ungrouped(DeviceBatch* out) {  // aggregate.rs:745-784
   uint64_t hs[2 * kMaxAccsTotal];
@@ -320,7 +180,7 @@ Status AggregateRelation::Impl::emit_grouped(DeviceBatch* out, int64_t expected)
     if (dk || dtype_width(dt) != 8)
       DFX_HIP(launch_compact(plane, 8, (const uint64_t*)mask.get(), (const uint64_t*)offsets.get(), n_slots, dense.get(), 0, s, (uint64_t)g));
     if (dk) {  // ids -> Arrow Utf8
-      DFX_RETURN_IF_ERROR(dict_emit(*dk, (const uint64_t*)dense.get(), g, &c));
+      DFX_RETURN_IF_ERROR(dk->dict.to_utf8((const uint64_t*)dense.get(), g, nullptr, 0, "Utf8 group keys", &c));
       continue;
     }
     auto vals = device_alloc((size_t)std::max<int64_t>(g, 1) * dtype_width(dt), &st);

@@ -3,8 +3,9 @@
 //   dfx_aggregate.cpp           set-up, chunks of accumulators, explain, next, drain
 //   dfx_aggregate_strategy.cpp  one batch through the strategy state machine (Phase, StrategyDecision)
 //   dfx_aggregate_table.cpp     table, spill list, routing regions (Pass2Window), launches, control-block checks (CtrlPipeline)
-//   dfx_aggregate_emit.cpp      Utf8 key dictionary, the key column ahead of time (EarlyKeys), the result batch
+//   dfx_aggregate_emit.cpp      the key column ahead of time (EarlyKeys), the result batch
 //   dfx_aggregate_partial.cpp   multi-GPU export / import
+// The Utf8 key dictionaries are Utf8Dict (dfx_utf8_dict.hpp), shared with the distinct-set aggregates.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -15,6 +16,7 @@
 
 #include "dfx_relation.hpp"
 #include "dfx_sigs.hpp"
+#include "dfx_utf8_dict.hpp"
 
 namespace dfx {
 
@@ -115,10 +117,7 @@ struct AggregateRelation::Impl {
     int key = 0;       // index among the GROUP BY expressions
     int src_col = 0;   // the Utf8 column of the input schema
     int virt_col = 0;  // its UInt64 id column in `bind_schema`
-    DevDict D;
-    std::shared_ptr<void> state, hash, sid, str_off, str_len, pool, cursors;
-    uint64_t ids_used = 0, pool_used = 0;  // as of the last completed batch
-    bool allocated = false;
+    Utf8Dict dict{"Utf8 key dictionary"};
   };
   std::vector<DictKey> dicts;
   SchemaInfo bind_schema;                  // input schema + the virtual id columns + the string terms' Boolean columns (what the program binds to)
@@ -387,9 +386,6 @@ struct AggregateRelation::Impl {
   Status settle_ctrl();
   Status handle_ctrl(const uint32_t* hc, int64_t n);
   Status finish_launched(int64_t rows, bool read_back = true);
-  Status dict_alloc(DictKey& d, int slots_log2, uint64_t pool_cap, bool keep);
-  Status dict_encode(DictKey& d, const DeviceColumn& src, int64_t n, DeviceColumn* ids_col);
-  Status dict_emit(const DictKey& d, const uint64_t* ids, int64_t g, DeviceColumn* out);
   ~Impl() {
     if (ctl.pending[0] || ctl.pending[1]) (void)hipStreamSynchronize(ctx().aux);  // snapshots still in flight
     for (int i = 0; i < 2; ++i) {

@@ -179,25 +179,7 @@ Status AggregateRelation::exchange_import_finish() {
 
 // the strings of dictionary d in local-id order (lengths + bytes back to back)
 Status AggregateRelation::exchange_dict_local(int d, std::vector<uint32_t>* lens, std::vector<uint8_t>* pool) {
-  Impl& m = *impl_;
-  const Impl::DictKey& k = m.dicts[(size_t)d];
-  lens->assign((size_t)k.ids_used, 0);
-  pool->clear();
-  if (!k.allocated || k.ids_used == 0) return Status::OK();
-  std::vector<uint64_t> offs((size_t)k.ids_used);
-  std::vector<uint8_t> raw((size_t)k.pool_used);
-  DFX_HIP(hipStreamSynchronize(ctx().stream));
-  DFX_HIP(hipMemcpy(lens->data(), k.D.str_len, sizeof(uint32_t) * lens->size(), hipMemcpyDeviceToHost));
-  DFX_HIP(hipMemcpy(offs.data(), k.D.str_off, sizeof(uint64_t) * offs.size(), hipMemcpyDeviceToHost));
-  if (!raw.empty()) DFX_HIP(hipMemcpy(raw.data(), k.D.pool, raw.size(), hipMemcpyDeviceToHost));
-  size_t total = 0;
-  for (uint32_t l : *lens) total += l;
-  pool->reserve(total);
-  for (size_t i = 0; i < lens->size(); ++i) {  // the pool is filled by atomics: put the strings in id order
-    if (offs[i] + (*lens)[i] > raw.size()) return Status::Err(DFX_INTERNAL_ERROR, "Utf8 key dictionary: string outside the pool");
-    pool->insert(pool->end(), raw.begin() + (ptrdiff_t)offs[i], raw.begin() + (ptrdiff_t)(offs[i] + (*lens)[i]));
-  }
-  return Status::OK();
+  return impl_->dicts[(size_t)d].dict.download(lens, pool);
 }
 
 // installs the GLOBAL dictionary (strings by global id: lens + bytes back to back) as dictionary d and rewrites the key
@@ -217,27 +199,7 @@ Status AggregateRelation::exchange_dict_globalise(int d, const std::vector<uint3
     DFX_HIP(launch_dict_remap_plane(plane, m.T.mask + 2, (const uint64_t*)dremap.get(), (uint64_t)remap.size(), s));
     DFX_HIP(hipStreamSynchronize(s));  // dremap dies with this scope
   }
-  const uint64_t g = lens.size();
-  int lg = 4;
-  while ((1ull << lg) / 2 < std::max<uint64_t>(g, 1) && lg < 31) ++lg;
-  k.ids_used = k.pool_used = 0;
-  DFX_RETURN_IF_ERROR(m.dict_alloc(k, lg, std::max<uint64_t>(pool.size(), 64), false));
-  std::vector<uint64_t> offs((size_t)g);
-  uint64_t at = 0;
-  for (size_t i = 0; i < (size_t)g; ++i) {
-    offs[i] = at;
-    at += lens[i];
-  }
-  if (g) {
-    DFX_HIP(hipMemcpy(k.D.str_len, lens.data(), sizeof(uint32_t) * (size_t)g, hipMemcpyHostToDevice));
-    DFX_HIP(hipMemcpy(k.D.str_off, offs.data(), sizeof(uint64_t) * (size_t)g, hipMemcpyHostToDevice));
-    if (!pool.empty()) DFX_HIP(hipMemcpy(k.D.pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
-  }
-  k.ids_used = g;
-  k.pool_used = pool.size();
-  const uint64_t hc[DICT_WORDS] = {k.pool_used, k.ids_used, 0, 0};
-  DFX_HIP(hipMemcpy(k.D.cursors, hc, sizeof(hc), hipMemcpyHostToDevice));
-  return Status::OK();
+  return k.dict.install(lens, pool);
 }
 
 Status AggregateRelation::ungrouped_select_chunk(int c) {

@@ -90,7 +90,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b, int64_
     for (DictKey& d : dicts) {
       if (d.src_col >= (int)b.columns.size() || b.columns[d.src_col].dtype != DFX_UTF8)
         return Status::Err(DFX_INTERNAL_ERROR, "GROUP BY key column is not Utf8 in this batch");
-      DFX_RETURN_IF_ERROR(dict_encode(d, b.columns[d.src_col], n, &ab.columns[d.virt_col]));
+      DFX_RETURN_IF_ERROR(d.dict.encode(b.columns[d.src_col], n, opt().dict_capacity_log2, &ab.columns[d.virt_col]));
     }
     if (terms_now) {
       const std::vector<Utf8TermSpec>& ts = pred_terms.terms();

@@ -1,5 +1,6 @@
-// dfx_relation.cpp -- what the operator units share (dfx_filter.cpp, dfx_project.cpp, dfx_aggregate*.cpp): the control
-// block's error word, the byte count of a fused program's input, the option list of a *_new_with_options call.
+// dfx_relation.cpp -- what the operator units share (dfx_filter.cpp, dfx_project.cpp, dfx_aggregate*.cpp, dfx_distinct_emit.cpp):
+// the control block's error word, a small upload, the byte count of a fused program's input, the option list of a
+// *_new_with_options call.
 #include "dfx_relation.hpp"
 
 namespace dfx {
@@ -30,6 +31,15 @@ Status take_ctrl_error(const std::shared_ptr<void>& ctrl, hipStream_t s) {
   DFX_HIP(hipMemcpyAsync(&errbits, (uint32_t*)ctrl.get() + CTRL_ERROR, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   DFX_HIP(hipStreamSynchronize(s));
   return errbits ? clear_ctrl_error(ctrl, errbits, s) : Status::OK();
+}
+
+Status upload_small(const void* host, size_t bytes, std::shared_ptr<void>* dev) {
+  Status st;
+  *dev = device_alloc(std::max<size_t>(bytes, 8), &st);
+  if (!*dev) return st;
+  DFX_HIP(hipMemcpyAsync(dev->get(), host, bytes, hipMemcpyHostToDevice, ctx().stream));
+  DFX_HIP(hipStreamSynchronize(ctx().stream));
+  return Status::OK();
 }
 
 double program_input_bytes(const ProgramBuilder& builder, const DeviceBatch& batch, int64_t n) {

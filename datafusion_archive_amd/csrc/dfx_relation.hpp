@@ -163,6 +163,9 @@ Status alloc_zeroed_ctrl(std::shared_ptr<void>* ctrl);
 Status clear_ctrl_error(const std::shared_ptr<void>& ctrl, uint32_t bits, hipStream_t stream);
 // reads CTRL_ERROR back (pageable 4-byte copy, one synchronisation of `stream`); non-zero: clear_ctrl_error
 Status take_ctrl_error(const std::shared_ptr<void>& ctrl, hipStream_t stream);
+// a few host bytes (a one-row result's value or validity word) in a device buffer of their own, copied on the library's stream
+// (it is non-blocking: a plain hipMemcpy would not wait for its work) and complete on return
+Status upload_small(const void* host, size_t bytes, std::shared_ptr<void>* dev);
 // bytes of `batch` that the program of `builder` reads over n rows (what the launchers report to the profiler)
 double program_input_bytes(const ProgramBuilder& builder, const DeviceBatch& batch, int64_t n);
 

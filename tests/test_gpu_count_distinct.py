@@ -12,6 +12,7 @@ from datafusion_archive_amd import _ffi
 from datafusion_archive_amd import execution as ex
 from datafusion_archive_amd.logicalplan import AggregateFunction, BinaryExpr, Column, DataType, Literal, Operator, ScalarValue
 from gpu_util import assert_arrays_identical
+from utf8_minmax_truth import encoded, utf8_extrema
 
 pytestmark = pytest.mark.gpu
 
@@ -307,3 +308,57 @@ def test_exchange_is_not_implemented():
     code = _ffi.lib().dfx_aggregate_exchange(ctypes.byref(rel._live_stream()), None, stats, err, 1024)
     assert code == 5 and b"COUNT_DISTINCT" in err.value
     assert as_dict(rel.next(), 1, 1) == {(1,): 1, (2,): 1, (3,): 1}  # the stream itself still runs
+
+
+def test_utf8_dictionaries_grow_under_the_distinct_sets():
+    """Both dictionaries of a distinct query -- the Utf8 key column's and the Utf8 argument's, whose ids carry the source's validity --
+    start with 16 slots (8 ids), so the slot and id tables of each grow several times while ids already sit in the sets.  (The string
+    pool does not: its floor of 64 KiB holds all of this data, one-row first batch or not.)"""
+    rng = np.random.default_rng(17)
+    n = 6000
+    kwords = ["key-%02d-%s" % (i, "é" * (i % 3)) for i in range(40)]
+    special = ["", "8 bytes!", "sixteen bytes !!", "seventeen bytes !", "日本語", "éü", "forty bytes " + "x" * 28]
+    assert [len(w.encode()) for w in special[1:4] + special[-1:]] == [8, 16, 17, 40]
+    swords = special + ["%s%03d" % ("abcdefghijklmnopqrstuvw"[: i % 23], i) for i in range(700 - len(special))]
+    k = [kwords[i] for i in rng.integers(0, len(kwords), n)]
+    s = [swords[i] for i in rng.integers(0, len(swords), n)]
+    k[:len(special)] = [kwords[1]] * len(special)
+    s[:len(special)] = special
+    valid = rng.random(n) > 0.1
+    valid[:len(special)] = True
+    s = [None if kk == kwords[0] or not ok else ss for kk, ss, ok in zip(k, s, valid)]  # one group has no non-null s
+    v = rng.integers(-1000, 1000, n).astype(np.int64)
+    schema = pa.schema([("k", pa.string()), ("s", pa.string()), ("v", pa.int64())])
+    table = pa.Table.from_arrays([pa.array(k, pa.string()), pa.array(s, pa.string()), pa.array(v)], schema=schema)
+    batches = [b for at, m in ((0, 1), (1, 1499), (1500, 2750), (4250, 1750)) for b in table.slice(at, m).to_batches()]
+    assert [b.num_rows for b in batches] == [1, 1499, 2750, 1750]
+    options = {"agg.dict_capacity_log2": 4, "agg.distinct_capacity_log2": 6}
+    str_min = AggregateFunction("MIN", [Column(1)], DataType.Utf8)
+    str_max = AggregateFunction("MAX", [Column(1)], DataType.Utf8)
+    total = AggregateFunction("SUM", [Column(2)], DataType.Int64)
+    sets = {}
+    for kk, ss in zip(k, s):
+        sets.setdefault(kk.encode(), set())
+        if ss is not None:
+            sets[kk.encode()].add(ss)
+    assert len(sets) == 40 and 600 < len(set().union(*sets.values())) <= 700 and not sets[kwords[0].encode()]
+    # GROUP BY k
+    got = _sorted(run(schema, batches, [Column(0)], [cd(1), str_min, str_max, total], options=options), 1).combine_chunks().to_batches()[0]
+    keys = encoded(got.column(0))
+    assert dict(zip(keys, got.column(1).to_pylist())) == {kk: len(vals) for kk, vals in sets.items()}
+    want = {(kt[0].encode(),): e for kt, e in utf8_extrema([k], s).items()}
+    assert dict(zip([(kk,) for kk in keys], zip(encoded(got.column(2)), encoded(got.column(3))))) == want
+    assert want[(kwords[0].encode(),)] == (None, None) and got.column(2).null_count == 1 and got.column(3).null_count == 1
+    base = _sorted(run(schema, batches, [Column(0)], [total], options=options), 1)
+    assert encoded(base.column(0).combine_chunks()) == keys
+    assert_arrays_identical(got.column(4), base.column(1), "SUM(v) grouped")
+    # ungrouped
+    got = run(schema, batches, [], [cd(1), str_min, str_max, total], options=options)
+    assert got.num_rows == 1 and got.column(0).to_pylist() == [len(set().union(*sets.values()))]
+    assert (encoded(got.column(1))[0], encoded(got.column(2))[0]) == utf8_extrema([], s)[()]
+    base = run(schema, batches, [], [total], options=options)
+    assert_arrays_identical(got.column(3), base.column(0), "SUM(v) ungrouped")
+    # one dictionary serves a key and an argument
+    ks = pa.schema([("k", pa.string()), ("v", pa.int64())])
+    got = run(ks, [b.select([0, 2]) for b in batches], [Column(0)], [cd(0)], options=options)
+    assert sorted(encoded(got.column(0))) == sorted(sets) and got.column(1).to_pylist() == [1] * 40
