@@ -158,7 +158,7 @@ struct Counters {
   long long xchg_wait_peers_us = 0;  // the first agreement round: mostly waiting for the slowest rank's local phase
   long long xchg_rounds = 0;         // collective rounds of the grouped exchanges (2 per query: the all-gather of states + counts, the buckets)
   long long xchg_host_syncs = 0;     // ... and their host synchronisations (2 per query)
-  long long xchg_exchange_us = 0;    // counts, buffers, payload rounds, merge kernels, the closing agreement
+  long long xchg_exchange_us = 0;    // after round 1's read-back: the plan, a second allocation if needed, payload rounds, merge kernels, the trailers
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
   // COUNT(DISTINCT) (dfx_distinct.cpp)
   long long distinct_set_growths = 0;  // distinct sets rehashed into larger ones

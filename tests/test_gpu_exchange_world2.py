@@ -88,6 +88,23 @@ def test_a_local_failure_at_any_stage_ends_the_exchange_on_every_rank(case, worl
         assert f"rank {r}: error: ExecutionError" in logs[r] and "rank 1 failed" in logs[r], logs[r]
 
 
+# (collective rounds, host synchronisations) the counters xchg_rounds / xchg_host_syncs show after one exchange, at world 2 and 3
+# alike.  Round 6: the grouped exchange is TWO collective rounds (the all-gather of states + counts, the buckets) and two host
+# synchronisations; a round more per further chunk of accumulators (more than 8); the lopsided case adds the agreement after
+# the second allocation (one round, one read-back); Utf8 keys add the agreement in front (a round, a read-back) and four
+# read-backs per dictionary (sizes, agreement, blobs, agreement).  The ungrouped form never adds to these counters.
+ROUNDS_AND_SYNCS = {
+    "int_keys_4_aggs": (2, 2), "int_keys_partitioned": (2, 2), "int_keys_lopsided": (3, 3), "eleven_accumulators": (3, 2),
+    "utf8_key": (3, 7), "utf8_and_int_keys": (3, 7), "ungrouped": (0, 0), "eleven_accumulators_ungrouped": (0, 0),
+}
+
+
+def _assert_rounds_and_syncs(case, world, logs):
+    rounds, syncs = ROUNDS_AND_SYNCS[case]
+    for r in range(world):
+        assert f"collective rounds {rounds}, host syncs {syncs}\n" in logs[r], logs[r]
+
+
 @pytest.mark.parametrize("world", [2, 3])
 @pytest.mark.parametrize("case", [c for c in xc.CASES if c not in xc.FAILURE_CASES])
 def test_library_exchange_between_processes(case, world, tmp_path):
@@ -102,6 +119,7 @@ def test_library_exchange_between_processes(case, world, tmp_path):
     if not group:  # every rank emits the global row
         for r in range(world):
             assert_batches_identical(got[r], want, f"{case} world={world} rank {r}")
+        _assert_rounds_and_syncs(case, world, logs)
         return
     # grouped: every group is emitted by exactly one rank
     present = [b for b in got if b is not None and b.num_rows]
@@ -109,11 +127,4 @@ def test_library_exchange_between_processes(case, world, tmp_path):
     assert sum(b.num_rows for b in present) == want.num_rows, f"{case}: {[b.num_rows for b in present]} groups emitted, oracle has {want.num_rows}\n" + "\n".join(logs)
     assert_groups_identical(union, want, len(group), f"{case} world={world}")
     assert all(b.num_rows > 0 for b in present) and len(present) == world, "every rank owns some groups"
-    # round 6: the grouped exchange is TWO collective rounds (the all-gather of states + counts, the buckets) and two host
-    # synchronisations; a round more per further chunk of accumulators (more than 8); Utf8 keys add their dictionary rounds
-    if case in ("int_keys_4_aggs", "int_keys_partitioned"):
-        for r in range(world):
-            assert "collective rounds 2, host syncs 2" in logs[r], logs[r]
-    if case == "int_keys_lopsided":  # + the agreement after the second allocation (one round, one read-back)
-        for r in range(world):
-            assert "collective rounds 3, host syncs 3" in logs[r], logs[r]
+    _assert_rounds_and_syncs(case, world, logs)
