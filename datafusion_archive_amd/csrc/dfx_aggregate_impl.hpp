@@ -310,6 +310,11 @@ struct AggregateRelation::Impl {
   // decided != nullptr: return as soon as the strategy is decided; *decided = the rows of b that are done by then
   Status consume_batch_chunk(const DeviceBatch& b, int64_t* decided = nullptr);
   Status launch_rows(const DeviceBatch& b, const DevProgram& prog, const DevColumns& cols, int64_t row0, int64_t n);
+  // The key column's Int32 shadow (agg.key_shadow; dfx_key_shadow.hpp): the 4-byte words of the key rows this bound batch starts at,
+  // or null -- no resident table below, another shape, wide keys, nulls, the option, memory.  The query's first question may build it.
+  const uint32_t* key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt);
+  bool key_shadow_asked = false;
+  int64_t key_shadow_launches = 0;  // (explain)
   Status drain();
   Status emit_grouped(DeviceBatch* out, int64_t expected);
   std::shared_ptr<void> emit_total;  // pinned: the scan's group count

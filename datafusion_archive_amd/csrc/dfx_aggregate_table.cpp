@@ -485,6 +485,48 @@ Status AggregateRelation::Impl::finish_launched(int64_t rows, bool read_back) {
   return handle_ctrl(hc, rows);
 }
 
+const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) {
+  const AggOptions& o = opt();
+  if (o.key_shadow == 0 || calibrating || !dec.narrow || kw != 1 || !fp.valid || prog.has_nulls || !input) return nullptr;
+  const int ks = fp.keycol[0];
+  if (ks >= prog.n_cols || prog.col_dtype[ks] != T_I64 || cols.c[ks].validity) return nullptr;
+  if (!partition_key_shadow_supported(prog, fp, cols, T, pt)) return nullptr;  // (no pass-1 kernel reads this shape's key from 4-byte words)
+  ScanMemo* memo = input->scan_memo();
+  if (!memo) return nullptr;
+  hipStream_t s = ctx().stream;
+  KeyShadowDevice dev;
+  dev.free_bytes = []() -> size_t {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return free_b;
+  };
+  dev.alloc = [](size_t bytes) { return device_alloc_optional(bytes); };
+  dev.narrow = [s](const void* src, int64_t rows, void* dst, uint32_t* dropped) -> bool {
+    ScopedUs t_build(&counters().agg_key_shadow_build_us);
+    std::shared_ptr<void> word = device_alloc_optional(sizeof(uint32_t));
+    if (!word) return false;
+    bool ok = hipMemsetAsync(word.get(), 0, sizeof(uint32_t), s) == hipSuccess;
+    ok = ok && launch_narrow_keys((const uint64_t*)src, rows, (uint32_t*)dst, (uint32_t*)word.get(), s) == hipSuccess;
+    ok = ok && hipMemcpyAsync(dropped, word.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = ok && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    return ok;
+  };
+  // what this query holds: routing regions and counts, the spill list, the table's key and accumulator planes
+  int widest = na();
+  for (const Chunk& ch : chunks) widest = std::max(widest, ch.n);
+  const size_t query_bytes = win.rows_bytes + win.cnt_bytes + (size_t)spill.capacity * 8 * (size_t)(kw + widest) + ((size_t)T.mask + 2) * 8 * (size_t)(kw + widest);
+  const bool first = !key_shadow_asked;
+  key_shadow_asked = true;
+  bool built = false;
+  const uint32_t* words = memo->key_shadows.acquire(cols.c[ks].values, o.key_shadow, first, query_bytes, dev, &built);
+  if (built) ++counters().agg_key_shadow_builds;
+  return words;
+}
+
 Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgram& prog_in, const DevColumns& cols_in,
                                             int64_t row0, int64_t n) {
   hipStream_t s = ctx().stream;
@@ -510,6 +552,17 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
     const DevFastPlan fpp = fast_plan();
     DevPartition pt = PT;
     if (win.pending > 0) pt.flags |= PTF_RESUME;
+    // the key column's Int32 shadow, bound in place of the column for this launch: 12 bytes per row.  Everything behind the
+    // hash image -- routed rows, pass 2, the table, the result's Int64 key column -- is what it was
+    if (const uint32_t* key_words = key_shadow_words(prog_in, fpp, cols_in, pt)) {
+      const int ks = fpp.keycol[0];
+      cols.c[ks].values = key_words + row0;
+      prog.col_dtype[ks] = T_U32;
+      pt.flags |= PTF_KEY4;
+      bytes -= 4.0 * (double)n;
+      ++counters().agg_key_shadow_launches;
+      ++key_shadow_launches;
+    }
     // close the window when one more batch could overflow a region (or the batch budget is used up; the calibration
     // slice is aggregated at once: the strategy decision reads the group count)
     const int max_batches = pair_scan() ? std::min(2, std::max(1, opt().partition_defer_batches)) : std::max(1, opt().partition_defer_batches);  // (pair scan: the spill list's sizing)

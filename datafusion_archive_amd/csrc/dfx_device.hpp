@@ -314,6 +314,10 @@ enum : uint32_t {
                           // (DevPartition::pair_plane / pair_operand) over the same regions: each launch is the one-value kernel with its
                           // 96 KB block.  Two aggregates: the scan transforms each operand for its accumulator; more (+ PTF_PLANES): raw
                           // operands, the transform in pass 2 (DevPartition::pair_ops)
+  PTF_KEY4 = 512u,        // with PTF_WS: the key column is bound to its Int32 shadow (4-byte words, every key below 2^32: the whole
+                          // column was checked when the shadow was built).  The scanners of the two compile-time signatures load two keys per
+                          // lane (StaticKey4Policy); the scan plan's kernels (PTF_PAIR included) load one 4-byte key per lane.
+                          // Set per launch (launch_rows), never part of the layout
   PTF_NARROW = 8u         // keys below 2^32 (seen by the calibration slice): 12-byte routed rows {hash image, operand}, pass 2
                           // works on 32-bit images; needs ring flavour, one key word, one aggregate
 };

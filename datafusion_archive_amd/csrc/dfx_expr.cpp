@@ -797,7 +797,7 @@ bool scan_plan_shape_ok(const DevProgram& P, const DevFastPlan& F, int kw, int n
 }
 
 bool bind_scan_plan(const DevProgram& P, const DevFastPlan& F, const DevColumns& C, int kw, int na, const uint8_t* val_xform,
-                    bool fixed, DevFastPlan* Fout, DevColumns* Cout) {
+                    bool fixed, DevFastPlan* Fout, DevColumns* Cout, bool key4_slots) {
   if ((F.plan_mode & 3) == 0 || !scan_plan_shape_ok(P, F, kw, na, val_xform)) return false;
   if (fixed && (kw != 1 || na < 1)) return false;
   const uint8_t* ones = device_ones_block();
@@ -818,6 +818,9 @@ bool bind_scan_plan(const DevProgram& P, const DevFastPlan& F, const DevColumns&
     src_of[n] = ac;  // (the key column again when the aggregate is over the key: read twice, a cache hit)
     if (slot_of[ac] < 0) slot_of[ac] = n;
     ++n;
+  } else if (key4_slots && kw == 1) {  // (slot look-ups: any order is right; the 4-byte-key kernels load slot 0 as the key)
+    src_of[n] = F.keycol[0];
+    slot_of[F.keycol[0]] = n++;
   }
   for (int c = 0; c < P.n_cols; ++c) {
     if (slot_of[c] >= 0) continue;
@@ -882,6 +885,21 @@ bool bind_scan_plan(const DevProgram& P, const DevFastPlan& F, const DevColumns&
     if (only_key) {
       gen = (gen & ~1) | 4;
       for (int sl = n; sl < kPlanCols; ++sl) {  // unused slots are read 8 bytes wide here: repeat slot 1, never the 4-byte key
+        Cout->c[sl] = Cout->c[1];
+        S.col_meta[sl] = S.col_meta[1];
+      }
+    }
+  }
+  // ... and of a slot look-up binding whose caller has kernels for it (key4_slots: the pair scan over the key's Int32 shadow)
+  if (!fixed && key4_slots && (gen & 1) && kw == 1 && n >= 2 && slot_of[F.keycol[0]] == 0) {
+    bool only_key = P.col_dtype[src_of[0]] == T_I32 || P.col_dtype[src_of[0]] == T_U32;
+    for (int sl = 1; sl < n && only_key; ++sl) {
+      const uint8_t t = P.col_dtype[src_of[sl]];
+      if (t == T_I32 || t == T_U32 || t == T_F32) only_key = false;
+    }
+    if (only_key) {
+      gen = (gen & ~1) | 4;
+      for (int sl = n; sl < kPlanCols; ++sl) {
         Cout->c[sl] = Cout->c[1];
         S.col_meta[sl] = S.col_meta[1];
       }

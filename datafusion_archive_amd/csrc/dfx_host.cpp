@@ -233,7 +233,7 @@ struct Pool {
   static constexpr size_t kSpareBudget = (size_t)1 << 30;
   size_t spare_bytes = 0;  // (only read / written on the allocation path of the pinned pool)
   int inject_oom = 0;      // test hook, see take()
-  void* take(size_t bytes, hipError_t* e) {
+  void* take(size_t bytes, hipError_t* e, bool retry = true) {
     {
       std::lock_guard<std::mutex> lk(mu);
       auto it = free_list.lower_bound(bytes);
@@ -251,7 +251,8 @@ struct Pool {
     } else {
       *e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
     }
-    if (*e != hipSuccess) {  // release cached blocks and retry once
+    if (*e != hipSuccess && !retry) (void)hipGetLastError();  // (optional work: the caller does without; no sticky error left behind)
+    if (*e != hipSuccess && retry) {  // release cached blocks and retry once
       // The failed attempt stays in HIP's sticky last-error slot: cleared here, or the next launch_* that returns
       // hipGetLastError() reports "out of memory" for a kernel that launched correctly (found by tools/soak.py: a long-running
       // process with many table sizes fills HBM with cached blocks, the first miss after that trims the pool and succeeds).
@@ -298,7 +299,7 @@ Pool& pin_pool() {
   return *p;
 }
 
-std::shared_ptr<void> pool_alloc(Pool& pool, size_t bytes, Status* st) {
+std::shared_ptr<void> pool_alloc(Pool& pool, size_t bytes, Status* st, bool retry = true) {
   Status init = ensure_init();
   if (!init.ok()) {
     if (st) *st = init;
@@ -306,7 +307,7 @@ std::shared_ptr<void> pool_alloc(Pool& pool, size_t bytes, Status* st) {
   }
   const size_t cap = Pool::round_up(bytes ? bytes : 1);
   hipError_t e = hipSuccess;
-  void* p = pool.take(cap, &e);
+  void* p = pool.take(cap, &e, retry);
   if (!p) {
     if (st)
       *st = Status::Err(DFX_EXECUTION_ERROR, strfmt("%s allocation of %zu bytes failed: %s",
@@ -331,6 +332,7 @@ Counters& counters() {
 
 std::shared_ptr<void> device_alloc(size_t bytes, Status* st) { return pool_alloc(dev_pool(), bytes, st); }
 std::shared_ptr<void> pinned_alloc(size_t bytes, Status* st) { return pool_alloc(pin_pool(), bytes, st); }
+std::shared_ptr<void> device_alloc_optional(size_t bytes) { return pool_alloc(dev_pool(), bytes, nullptr, false); }
 void pool_trim() {
   dev_pool().trim();
   pin_pool().trim();

@@ -17,6 +17,7 @@
 
 #include "../../include/dfx.h"
 #include "dfx_device.hpp"
+#include "dfx_key_shadow.hpp"
 #include "dfx_utf8_match.hpp"
 
 namespace dfx {
@@ -159,6 +160,9 @@ struct Counters {
   long long xchg_rounds = 0;         // collective rounds of the grouped exchanges (2 per query: the all-gather of states + counts, the buckets)
   long long xchg_host_syncs = 0;     // ... and their host synchronisations (2 per query)
   long long xchg_exchange_us = 0;    // after round 1's read-back: the plan, a second allocation if needed, payload rounds, merge kernels, the trailers
+  long long agg_key_shadow_builds = 0;    // Int32 shadows of resident Int64 key columns built (once per table and column)
+  long long agg_key_shadow_launches = 0;  // pass-1 launches that read the key from its shadow (PTF_KEY4)
+  long long agg_key_shadow_build_us = 0;  // ... wall time of the builds (kernel + the read-back of the dropped-halves word)
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
   // COUNT(DISTINCT) (dfx_distinct.cpp)
   long long distinct_set_growths = 0;  // distinct sets rehashed into larger ones
@@ -178,6 +182,8 @@ Counters& counters();
 std::shared_ptr<void> device_alloc(size_t bytes, Status* st);
 // pooled pinned host memory for H2D / D2H staging
 std::shared_ptr<void> pinned_alloc(size_t bytes, Status* st);
+// ... for work the query does not need (the key shadow): one attempt -- no cached block is released for it, no retry
+std::shared_ptr<void> device_alloc_optional(size_t bytes);
 void pool_trim();
 void pool_inject_oom(int n);  // test hook (dfx_set_option "pool.inject_oom"): the next n device allocations fail their first attempt for real
 
@@ -255,6 +261,7 @@ struct Relation {
 };
 struct ScanMemo {  // shared by every scan of a resident table (a `mutable` member of a const TableData): guarded
   mutable std::mutex mu;
+  KeyShadows key_shadows;  // the Int32 copies of the table's null-free Int64 columns (dfx_key_shadow.hpp; its own lock)
   std::vector<std::pair<uint64_t, uint64_t>> calibrated_groups;  // (program fingerprint, groups in the first 2^18 rows)
   bool lookup(uint64_t fp, uint64_t* groups) const {
     std::lock_guard<std::mutex> lk(mu);

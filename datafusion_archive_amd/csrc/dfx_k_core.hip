@@ -783,6 +783,28 @@ __global__ void k_reduce_fold(const DevTable T, const uint8_t* __restrict__ arg_
 __global__ __launch_bounds__(kBlock) void k_fill_u64(uint64_t* __restrict__ p, uint64_t v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) p[i] = v;
 }
+// The Int32 shadow of an Int64 key column (dfx_key_shadow.hpp): 8 bytes read, 4 written per row -- a lane takes two keys (one
+// 16-byte load, one 8-byte store); the upper halves it drops are ORed into one word: non-zero = some key has no 32-bit form.
+__global__ __launch_bounds__(kBlock) void k_narrow_keys(const uint64_t* __restrict__ in, int64_t n, uint32_t* __restrict__ out, uint32_t* __restrict__ dropped) {
+  typedef uint64_t u64x2v __attribute__((ext_vector_type(2)));
+  typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+  uint32_t hi = 0;
+  const int64_t n2 = n >> 1;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kBlock) {
+    const u64x2v k = __builtin_nontemporal_load((const u64x2v*)in + i);
+    hi |= (uint32_t)(k.x >> 32) | (uint32_t)(k.y >> 32);
+    u32x2v w;
+    w.x = (uint32_t)k.x;
+    w.y = (uint32_t)k.y;
+    ((u32x2v*)out)[i] = w;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint64_t k = in[n - 1];
+    hi |= (uint32_t)(k >> 32);
+    out[n - 1] = (uint32_t)k;
+  }
+  if (hi != 0) atomicOr(dropped, hi);
+}
 __global__ __launch_bounds__(kBlock) void k_fill_u32(uint32_t* __restrict__ p, uint32_t v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) p[i] = v;
 }
@@ -1330,6 +1352,12 @@ hipError_t launch_fill_u64(uint64_t* p, uint64_t v, int64_t n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   Scope sc(KID_FILL, s, 0);
   hipLaunchKernelGGL(k_fill_u64, dim3(stream_grid((n + kBlock - 1) / kBlock, 8)), dim3(kBlock), 0, s, p, v, n);
+  return hipGetLastError();
+}
+hipError_t launch_narrow_keys(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* dropped, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  Scope sc(KID_FILL, s, 12.0 * (double)n);
+  hipLaunchKernelGGL(k_narrow_keys, dim3(stream_grid((n / 2 + kBlock) / kBlock, 8)), dim3(kBlock), 0, s, in, n, out, dropped);
   return hipGetLastError();
 }
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, int64_t n, hipStream_t s) {

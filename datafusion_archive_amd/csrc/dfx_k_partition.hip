@@ -802,13 +802,31 @@ void launch_partition_variant21(DFX_PARTITION_VARIANT_ARGS);  // 3 columns
 void launch_partition_variant22(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, 4-byte columns
 void launch_partition_variant23(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, validity bitmaps
 void launch_partition_variant24(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, both
+void launch_partition_variant25(DFX_PARTITION_VARIANT_ARGS);  // the headline's signature over the key column's Int32 shadow (two keys per lane)
+void launch_partition_variant26(DFX_PARTITION_VARIANT_ARGS);  // ... key + SUM without a predicate
+void launch_partition_variant29(DFX_PARTITION_VARIANT_ARGS);  // the pair scan, 3 columns, a 4-byte key (one 4-byte load per lane: three row groups per trip have no pairs)
+void launch_partition_variant30(DFX_PARTITION_VARIANT_ARGS);  // ... 4 columns
+
+// The Int32 shadow of the key column (PTF_KEY4): which compile-time signature reads this program's key as 4-byte words, two per lane?
+// P, fast: the program as the operator bound it (the key an 8-byte integer column).  0: none -- the scan plan may still bind the
+// shadow (partition_key_shadow_supported).  (DFX_PARTITION_VARIANT_WS_ONLY)
+static int partition_key_shadow_variant(const DevProgram& P, const DevFastPlan& fast, const DevTable& T, const DevPartition& PT) {
+  if (!(PT.flags & PTF_WS) || (PT.flags & PTF_PAIR) || !(PT.flags & PTF_NARROW) || (fast.plan_mode & 3) == 2 || T.kw != 1) return 0;
+  const bool shared = (PT.flags & PTF_SHARED) != 0;
+  const uint8_t raw_kind0[1] = {SigKeySumPred2F64::acc(0)}, raw_kind1[1] = {SigKeySum::acc(0)}, raw_xf[1] = {VT_RAW};
+  if (shared ? sig_matches<SigKeySumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf) : sig_matches<SigKeySumPred2F64>(P, fast, 1, T.na, T.acc_kind, T.val_xform))
+    return 25;
+  if (shared ? sig_matches<SigKeySum>(P, fast, 1, 1, raw_kind1, raw_xf) : sig_matches<SigKeySum>(P, fast, 1, T.na, T.acc_kind, T.val_xform)) return 26;
+  return 0;
+}
 
 // The scan plan (DevScanPlan): run-time shapes as data.  Which binding a launch needs follows from the kernel flavour that
 // will run: the one-value flavours (narrow rows, the wave-specialised kernel) find the key in slot 0 and the routed value in
 // slot 1 (PlanPolicy1), the others look their slots up.
+// dry: bind only -- would a launch go through?  (host only, no launch)
 static bool launch_partition_plan(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,
                                   const DevTable& T, const DevPartition& PT, const DevRows& spill, int64_t n, size_t lds_bytes,
-                                  hipStream_t s) {
+                                  hipStream_t s, bool dry = false) {
   const bool shared = (PT.flags & PTF_SHARED) != 0;
   const bool pair = (PT.flags & PTF_PAIR) != 0;  // two operands per routed row: the multi-value binding (slot look-ups) in the wave-specialised kernel
   const bool one_value = !pair && ((PT.flags & PTF_WS) || ((PT.mode & 15u) == 2 && (PT.flags & PTF_NARROW)));
@@ -817,7 +835,8 @@ static bool launch_partition_plan(const DevProgram& P, const DevFastPlan& fast, 
   const uint8_t raw_xf[kMaxAggs] = {VT_RAW};
   DevFastPlan fp;
   DevColumns cp;
-  if (!bind_scan_plan(P, fast, C, 1, shared ? 1 : T.na, shared ? raw_xf : T.val_xform, one_value, &fp, &cp)) return false;
+  // (a pair scan whose key is the only 4-byte column -- the Int32 shadow -- has kernels of its own: asked for under PTF_KEY4 alone)
+  if (!bind_scan_plan(P, fast, C, 1, shared ? 1 : T.na, shared ? raw_xf : T.val_xform, one_value, &fp, &cp, pair && (PT.flags & PTF_KEY4))) return false;
   typedef void (*Variant)(DFX_PARTITION_VARIANT_ARGS);
   // [> 2 columns][DevScanPlan::gen: bit 0 4-byte columns, bit 1 validity bitmaps, bit 2 (instead of bit 0) a 4-byte key only]
   static const Variant by_need[3][8] = {
@@ -827,13 +846,22 @@ static bool launch_partition_plan(const DevProgram& P, const DevFastPlan& fast, 
        launch_partition_variant19, launch_partition_variant22, launch_partition_variant20, launch_partition_variant24},
       {launch_partition_variant11, launch_partition_variant15, launch_partition_variant16, launch_partition_variant12,
        launch_partition_variant19, launch_partition_variant15, launch_partition_variant20, launch_partition_variant12}};
-  if (!one_value && (fp.scan.gen & 4)) return false;  // (cannot happen: bind_scan_plan gives bit 2 to fixed-slot bindings only)
+  if (!one_value && !pair && (fp.scan.gen & 4)) return false;  // (cannot happen: bind_scan_plan gives bit 2 to fixed-slot bindings and to the pair scan over a shadow)
+  // Over a shadow only the forms that load the key as a 4-byte word.  A second 4-byte slot -- COUNT(k) GROUP BY k binds the key
+  // twice -- would take the generic 4-byte-column form (the aligned 8 bytes that hold the element, a lane select), which the pair
+  // kernels ran at half the speed of the 8-byte key: such launches keep the 8-byte column.
+  if ((PT.flags & PTF_KEY4) && (fp.scan.gen & 7) != 4) return false;  // (pair scan: 10.2 ms against 5.5 ms of pass 1 per 10^9 rows)
   if (pair && fp.scan.n_cols != 3 && fp.scan.n_cols != 4) return false;  // (the pair kernels: key + two operand columns, and one more predicate column -- variants 21-24, 11 / 15 / 16 / 12)
   DevPartition PTp = PT;
   if (pair) {  // operand 1: the plan slot and the transform of its first accumulator
     const uint32_t a1 = PT.pair_arg1 < (uint32_t)kMaxAggs ? PT.pair_arg1 : 1u;
     PTp.pair_slot1 = fp.scan.argslot[a1];
     PTp.pair_xf1 = T.val_xform[a1];
+  }
+  if (dry) return true;
+  if (pair && (fp.scan.gen & 4)) {
+    (fp.scan.n_cols == 3 ? launch_partition_variant29 : launch_partition_variant30)(P, fp, cp, plan, T, PTp, spill, n, lds_bytes, s);
+    return true;
   }
   by_need[fp.scan.n_cols <= 2 ? 0 : fp.scan.n_cols == 3 ? 1 : 2][fp.scan.gen & 7](P, fp, cp, plan, T, PTp, spill, n, lds_bytes, s);
   return true;
@@ -847,6 +875,23 @@ bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, cons
   DevColumns cp;
   if (!bind_scan_plan(P, fast, C, 1, T.na, T.val_xform, false, &fp, &cp)) return false;
   return (fp.scan.n_cols == 3 || fp.scan.n_cols == 4) && !(fp.scan.gen & 4);
+}
+
+// PTF_KEY4: does a pass-1 kernel read this program's key from 4-byte words?  P, fast, C: the batch as the operator bound it, the
+// key (slot ks) an 8-byte integer column without nulls; PT: the launch's flags.  The two compile-time signatures (two keys per
+// lane), or whatever the scan plan binds with the key as an unsigned 4-byte column: its one-value kernels (variants 17 and 19) and
+// the pair kernels (29 and 30), one 4-byte load per lane.  The plan
+// refuses what it cannot widen -- an aggregate over the key itself, a product --: those launches keep the 8-byte column.
+bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT) {
+  if (!(PT.flags & PTF_WS) || T.kw != 1 || !fast.valid) return false;
+  if (partition_key_shadow_variant(P, fast, T, PT)) return true;
+  const int ks = fast.keycol[0];
+  if (ks >= kMaxCols) return false;
+  DevProgram P4 = P;
+  P4.col_dtype[ks] = T_U32;  // (C's own 8-byte aligned base stands in for the shadow's)
+  DevPartition PT4 = PT;
+  PT4.flags |= PTF_KEY4;
+  return launch_partition_plan(P4, fast, C, DevAggPlan{}, T, PT4, DevRows{}, 0, 0, nullptr, true);
 }
 
 // PTF_PLANES: does THIS bound batch take the wave-specialised one-value pass 1 with the aggregates' common raw operand?
@@ -880,6 +925,16 @@ hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const 
   const bool shared = (PT.flags & PTF_SHARED) != 0;
   const uint8_t raw_kind0[1] = {SigKeySumPred2F64::acc(0)}, raw_kind1[1] = {SigKeySum::acc(0)}, raw_xf[1] = {VT_RAW};
   static_assert(SigKeySumPred2F64::xf(0) == VT_RAW && SigKeySum::xf(0) == VT_RAW, "the one-aggregate signatures route the raw operand");
+  if (PT.flags & PTF_KEY4) {  // (the host asked partition_key_shadow_variant first, with the 8-byte binding; C.c[key] is the shadow)
+    DevProgram P8 = P;
+    if (fast.valid && fast.keycol[0] < kMaxCols) P8.col_dtype[fast.keycol[0]] = T_I64;
+    switch (partition_key_shadow_variant(P8, fast, T, PT)) {
+      case 25: launch_partition_variant25(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); return hipGetLastError();
+      case 26: launch_partition_variant26(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); return hipGetLastError();
+      default: break;
+    }
+    return launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s) ? hipGetLastError() : hipErrorNotSupported;  // (the key an unsigned 4-byte column)
+  }
   if (PT.flags & PTF_PAIR)  // (the host asked partition_pair_supported first: a batch the plan cannot bind is its error to handle)
     return launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s) ? hipGetLastError() : hipErrorNotSupported;
   if ((fast.plan_mode & 3) == 2 && launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s)) return hipGetLastError();  // (A/B: scan.plan = 2)

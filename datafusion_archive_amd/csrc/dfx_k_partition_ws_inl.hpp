@@ -159,7 +159,9 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
             POL::eval(P, F, cur, curv, reg, rv, inb, err, prep);
             uint64_t pm = POL::template pass_mask<FORM>(P, F, plan.pred, cur, curv, reg, rv, prep);  // (evaluated for every lane)
             if constexpr (!FULL) pm &= __ballot(inb);
-            const uint64_t key = POL::key(P, F, plan.key[0], 0, cur, curv, reg, rv);
+            uint64_t key;
+            if constexpr (KeyPairsOf<POL>::value) key = POL::pair_key(col[u & ~1], u & 1, lane);  // (two keys per lane: StaticKey4Policy)
+            else key = POL::key(P, F, plan.key[0], 0, cur, curv, reg, rv);
             uint64_t v;
             bool valid;
             POL::arg(P, F, plan.arg[0], 0, cur, curv, reg, rv, v, valid);
@@ -364,6 +366,18 @@ void launch_partition_ws(const DevProgram& P, const DevFastPlan& fast, const Dev
       launch_partition_pol<POL, POLS, POLN>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                              \
   }
 
+
+// a policy that only the wave-specialised kernel knows (StaticKey4Policy): the host asks for it under PTF_WS alone
+#define DFX_PARTITION_VARIANT_WS_ONLY(ID, POLW, POLD)                                                                      \
+  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
+    launch_partition_ws<POLW, POLD>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                                      \
+  }
+
+// ... the PAIR flavour alone (the pair scan over a 4-byte key: PlanPolicyN with GENK = 4)
+#define DFX_PARTITION_VARIANT_WS_PAIR_ONLY(ID, POLP)                                                                       \
+  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
+    hipLaunchKernelGGL((k_partition_ws<POLP, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n); \
+  }
 
 // ... and, for the policies that can evaluate two arguments (POLP: slot look-ups, PlanPolicyN), the PAIR flavour (PTF_PAIR): always
 // eight scanners + eight routers (twelve routers' queues with two operand planes do not fit the LDS), the run-time comparison form

@@ -54,8 +54,9 @@ int device_cu_count();
 bool scan_plan_shape_ok(const DevProgram& P, const DevFastPlan& F, int kw, int na, const uint8_t* val_xform);
 // Per launch: the plan-order column binding (Cout) and the plan itself (Fout->scan) for the bound batch.  fixed: one key in
 // slot 0 and the (first) argument in slot 1 (PlanPolicy1).  False: the shape or this batch's buffers are not covered.
+// key4_slots: the caller has slot look-up kernels for "the key in slot 0 is the only 4-byte column" (DevScanPlan::gen bit 2).
 bool bind_scan_plan(const DevProgram& P, const DevFastPlan& F, const DevColumns& C, int kw, int na, const uint8_t* val_xform,
-                    bool fixed, DevFastPlan* Fout, DevColumns* Cout);
+                    bool fixed, DevFastPlan* Fout, DevColumns* Cout, bool key4_slots = false);
 
 // K1 predicate_mask: fused compare/AND/OR expression -> Arrow LSB bitmap (one __ballot per 64 rows)
 //   replaces comparison_ops!/boolean_ops!/literal_array! closures (expression.rs:171-243, :410-465)
@@ -123,6 +124,8 @@ hipError_t launch_merge_rows(const DevRows& rows, int64_t row_begin, int64_t n_r
                              const DevRows& spill, hipStream_t s);
 hipError_t launch_rehash(const DevTable& from, const DevTable& to, const DevRows& spill, hipStream_t s);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, int64_t n, hipStream_t s);
+// the low halves of n 8-byte keys (in: 16-byte aligned) as 4-byte words (out: 8-byte aligned); the OR of the dropped halves is ORed into *dropped
+hipError_t launch_narrow_keys(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* dropped, hipStream_t s);
 // device -> host-mapped pinned memory by a kernel on `s` (falls back to hipMemcpyAsync for unaligned pointers)
 hipError_t launch_copy_to_host(const void* src_device, void* dst_pinned, size_t bytes, hipStream_t s);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, int64_t n, hipStream_t s);
@@ -175,6 +178,7 @@ hipError_t launch_mask_tile_counts(const uint64_t* mask_words, uint32_t* tile_co
 size_t partition_stage_bytes(const DevPartition& PT);
 bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PLANES: ... the one-value kernels with the raw operand
 bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PAIR: this bound batch fits the pair kernels
+bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT);  // PTF_KEY4: a pass-1 kernel reads this batch's key from its Int32 shadow
 hipError_t launch_probe_wide_keys(const DevTable& T, hipStream_t s);
 size_t partition_ring_bytes(uint32_t n_words, uint32_t n_parts, int ring_rows, bool hot = false, bool narrow = false, int queue_rows = 0);
 size_t partition_ws_bytes(uint32_t n_parts, int scanner_waves, int operands = 1);  // LDS of the wave-specialised pass-1 kernel (PTF_WS)

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "dfx_kernels.hpp"
 #include "dfx_sigs.hpp"
 
@@ -750,6 +752,61 @@ struct StaticPolicy {
   }
 };
 
+// A two-column signature whose KEY column is bound as 4-byte words: the Int32 shadow of a resident Int64 key column whose keys
+// are all below 2^32.  The scanner waves of k_partition_ws load two keys per lane: one 8-byte load per
+// lane covers the keys of TWO row groups (128 rows), next to the two 8-byte operand loads of those rows -- every column load
+// stays a 512-byte wave instruction, 12 bytes per row.  Row L of group 2j + b finds its key in lane 32 b + L / 2, half L & 1,
+// of pair word j (pair_key: two ds_bpermute and a select).  Trips start on even groups (U is even, row0 a multiple of 64 and
+// the binding 8-byte aligned), so a pair never straddles two trips.  Only the wave-specialised kernel knows this form.
+template <int U_, typename SIG>
+struct StaticKey4Policy : StaticPolicy<2, U_, SIG> {
+  typedef StaticPolicy<2, U_, SIG> Base;
+  typedef typename Base::COLV COLV;
+  static constexpr int U = U_;
+  static constexpr bool kKeyPairs = true;
+  static constexpr int KC = SIG::key_col(0);
+  static_assert(SIG::NCOL == 2 && SIG::KW == 1 && U_ % 2 == 0, "one operand column beside the key; whole pairs of row groups per trip");
+  static DEV void load(const DevProgram&, const DevColumns& C, int64_t row, bool inb, COLV& col, uint32_t& cv) {  // (one row: its own key, zero-extended)
+    cv = 0xFFFFFFFFu;
+    col[1 - KC] = __builtin_nontemporal_load((const uint64_t*)C.c[1 - KC].values + (inb ? row : 0));
+    col[KC] = (uint64_t)__builtin_nontemporal_load((const uint32_t*)C.c[KC].values + (inb ? row : 0));
+  }
+  // as StaticPolicy::load_trip; the key column: U / 2 pair words, col[2j][KC] = the keys of rows 128 j + 2 lane and + 1 of the trip.
+  // The pair index is clamped to the pair that holds the batch's last row: an odd batch reads four bytes past its last key (the
+  // next batch's first key, or the padding the shadow is allocated with).
+  static DEV void load_trip(const DevColumns& C, int64_t w0, bool active, int64_t n, int lane, COLV (&col)[U], uint32_t (&cv)[U]) {
+    const int64_t r0 = active ? w0 * 64 : 0;
+    const int64_t left = n - r0;
+    const bool none = !active || left <= 0;
+    const uint32_t last = none ? 0u : (uint32_t)((left < (int64_t)U * 64 ? left : (int64_t)U * 64) - 1);
+    const uint64_t* pv = (const uint64_t*)C.c[1 - KC].values + (none ? 0 : r0);
+    const uint64_t* pk = (const uint64_t*)((const uint32_t*)C.c[KC].values + (none ? 0 : r0));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      cv[u] = 0xFFFFFFFFu;
+      const uint32_t i = (uint32_t)(u * 64 + lane);
+      col[u][1 - KC] = __builtin_nontemporal_load(pv + (i < last ? i : last));
+      col[u][KC] = 0;
+    }
+    const uint32_t lastp = last >> 1;
+#pragma unroll
+    for (int j = 0; j < U / 2; ++j) {
+      const uint32_t i = (uint32_t)(j * 64 + lane);
+      col[2 * j][KC] = __builtin_nontemporal_load(pk + (i < lastp ? i : lastp));
+    }
+  }
+  // the key of this lane's row in group 2j + b of the trip, from pair word j (every lane of the wave takes part)
+  static DEV uint64_t pair_key(const COLV& pairs, int b, int lane) {
+    const uint64_t w = pairs[KC];
+    const int src = (b * 32 + (lane >> 1)) << 2;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)w);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(w >> 32));
+    return (uint64_t)((lane & 1) ? hi : lo);
+  }
+};
+template <typename POL, typename = void> struct KeyPairsOf { static constexpr bool value = false; };
+template <typename POL> struct KeyPairsOf<POL, std::enable_if_t<POL::kKeyPairs>> { static constexpr bool value = true; };
+
 // ---------------------------------------------------------------------------------------------
 // scan plan (DevScanPlan): the run-time shape family evaluated as DATA -- see dfx_device.hpp
 // ---------------------------------------------------------------------------------------------
@@ -787,7 +844,8 @@ DEV uint64_t plan_sel(const u64x16& reg, uint32_t slot) {  // slot is wave-unifo
 // GENK bit 0 (W4): 4-byte columns (read as the aligned 8 bytes that hold the element, widened afterwards), bit 1 (NULLS):
 // validity bitmaps (without either every column is 8 bytes wide and null-free: no widening, no validity loads);
 // FIXED: one key in slot 0, one routed argument in slot 1 (the partitioned GROUP BY's one-value kernels).
-// bit 2 (KEY4, FIXED kernels only): slot 0 -- the key -- is a 4-byte integer column and every other slot is 8 bytes wide: the
+// bit 2 (KEY4: the FIXED kernels, and the pair scan's slot look-ups over a key shadow -- PlanPolicyN<3, 3, 4> / <4, 2, 4>, whose
+// binding puts the key in slot 0): slot 0 -- the key -- is a 4-byte integer column and every other slot is 8 bytes wide: the
 // key is read with a real 4-byte load (half the bytes of the aligned-pair form, no lane select) and extended in one operation.
 // The reference's own GROUP BY fixtures have Int32 keys (aggregate.rs:1033-1127).
 constexpr int kPlanW4 = 1, kPlanNulls = 2, kPlanKey4 = 4;

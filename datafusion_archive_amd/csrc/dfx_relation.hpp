@@ -78,6 +78,9 @@ struct AggOptions {
   int narrow_chunk16 = 1;      // narrow rows are written in 16-row chunks (sector-aligned) when no hot-key pairs need the LDS
   int shared_operand = 1;      // 2..3 aggregates of one null-free operand over narrow keys: 12-byte routed rows {image, raw operand}
   int narrow_keys = -1;        // 12-byte routed rows when the calibration slice saw only keys below 2^32: -1 auto, 0 never
+  int key_shadow = -1;         // the Int32 shadow of a resident table's null-free Int64 key column (dfx_key_shadow.hpp: pass 1 reads 12 bytes per row
+                               // instead of 16): -1 built by the second query that qualifies on a table and column, 0 never (neither built nor
+                               // used), 1 built by the first
   int partition_layout = 1;    // routing scratch: 1 producer-major, 0 partition-major (round 1), 2 windowed (DevPartition::win_stride;
                                // measured no better for the filtered query and 17 % worse in pass 1 when every row is routed)
   int partition_producers = 0; // pass-1 workgroups of the ring flavour (0: one per CU)

@@ -54,6 +54,12 @@ Status TableScanRelation::next(DeviceBatch* out, bool* has) {
   return Status::OK();
 }
 
+// the columns a GROUP BY key's Int32 shadow can be made for (dfx_key_shadow.hpp): plain Int64, no nulls
+static void register_key_shadows(TableData* t) {
+  for (const DeviceColumn& c : t->columns)
+    if (c.dtype == DFX_INT64 && !c.absent && c.null_count == 0 && c.length == t->num_rows) t->memo.key_shadows.add_column(c.values, c.length);
+}
+
 namespace {
 
 // concatenates device batches column-wise into one resident table.  One batch is adopted as it is; several batches are
@@ -219,6 +225,7 @@ Status build_table(Relation* rel, std::shared_ptr<TableData>* out) {
     }
   }
   DFX_HIP(hipStreamSynchronize(s));
+  register_key_shadows(t.get());
   *out = t;
   return Status::OK();
 }
@@ -255,6 +262,7 @@ bool set_option_in(AggOptions& o, const char* key, int64_t value) {
   else if (!strcmp(key, "agg.hot_keys")) o.hot_keys = (int)value;
   else if (!strcmp(key, "agg.partition_layout")) o.partition_layout = (int)value;
   else if (!strcmp(key, "agg.narrow_keys")) o.narrow_keys = (int)value;
+  else if (!strcmp(key, "agg.key_shadow")) o.key_shadow = (int)value;
   else if (!strcmp(key, "agg.narrow_chunk16")) o.narrow_chunk16 = (int)value;
   else if (!strcmp(key, "agg.shared_operand")) o.shared_operand = (int)value;
   else if (!strcmp(key, "agg.ctrl_snapshot")) o.ctrl_snapshot = (int)value;
@@ -384,6 +392,7 @@ int32_t dfx_table_synth(const dfx_synth_column* cols, int32_t n_cols, uint64_t s
     }
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return to_c(Status::Err(DFX_EXECUTION_ERROR, hipGetErrorString(e)), err, errlen);
+    register_key_shadows(t.get());
     *out = new dfx_table{t};
     return DFX_OK;
   });
@@ -469,6 +478,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_pass2_launches")) return counters().agg_pass2_launches;
   if (!strcmp(name, "agg_pair_launches")) return counters().agg_pair_launches;
   if (!strcmp(name, "agg_plane_launches")) return counters().agg_plane_launches;
+  if (!strcmp(name, "agg_key_shadow_builds")) return counters().agg_key_shadow_builds;
+  if (!strcmp(name, "agg_key_shadow_launches")) return counters().agg_key_shadow_launches;
+  if (!strcmp(name, "agg_key_shadow_build_us")) return counters().agg_key_shadow_build_us;
   if (!strcmp(name, "agg_pair_fallbacks")) return counters().agg_pair_fallbacks;
   if (!strcmp(name, "agg_growths")) return counters().agg_growths;
   if (!strcmp(name, "agg_shared_operand_launches")) return counters().agg_shared_operand_launches;

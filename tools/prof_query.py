@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Runs one workload a few times (no CPU baseline): the target of rocprofv3 runs.
-usage: prof_query.py <headline|selNN|cfg3|cfg2|q1|neighbour|oneterm|threeterm|threecol|diffop|avgmax|product> [rows] [iters] [option=value ...]
+usage: prof_query.py <headline|selNN|cfg3|cfg2|q1|neighbour|oneterm|threeterm|threecol|diffop|avgmax|product|int32key|minonly> [rows] [iters] [option=value ...]
+(int32key: the headline query over an Int32 key column, 12 B/row; minonly: MIN(v) instead of SUM(v) -- the scan plan's kernels)
 (neighbour: SELECT k, SUM(v), MIN(v) WHERE v >= lo AND v < hi GROUP BY k -- two aggregates of one operand;
  oneterm: SELECT k, SUM(v) WHERE v < 204.8 GROUP BY k; threecol: SELECT k, SUM(w) WHERE v > lo AND v < hi GROUP BY k;
  product: SELECT k, SUM(v * 2.0) WHERE v > lo AND v < hi GROUP BY k -- shapes without a static signature: FastPolicy)"""
@@ -81,6 +82,12 @@ else:
         schema = pa.schema([("k", pa.int64()), ("v", pa.float64()), ("w", pa.float64())])
         aggs = [AggregateFunction("AVG", [Column(1)], f64), AggregateFunction("MAX", [Column(2)], f64)]
         bytes_per_row = 24
+    if wl == "int32key":
+        syn[0] = ("k", ex.SYNTH_I32_UNIFORM, 0, 1e6, 0.0)
+        schema = pa.schema([("k", pa.int32()), ("v", pa.float64())])
+        bytes_per_row = 12
+    if wl == "minonly":
+        aggs = [AggregateFunction("MIN", [Column(1)], f64)]
     if wl == "product":
         aggs = [AggregateFunction("SUM", [BinaryExpr(Column(1), Operator.Multiply, lit(2.0))], f64)]
     if wl.startswith("sel"):  # sel50 / sel80 / sel35 ...: the headline query keeping that share of the rows (v is uniform on [0, 1024))
