@@ -18,14 +18,17 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libdfx_hip.so")
 
+
+def _pass1_units() -> List[str]:
+    """the pass-1 units of the partitioned GROUP BY: the names in DFX_PASS1_UNITS (csrc/dfx_pass1_units.hpp), one translation unit each"""
+    import re
+    text = open(os.path.join(CSRC, "dfx_pass1_units.hpp")).read()
+    return re.findall(r"\bX\((\w+)\)", re.search(r"#define DFX_PASS1_UNITS\(X\)((?:.*\\\n)*.*)", text).group(1))
+
+
 # kernel translation units first (slowest): they compile in parallel
 SOURCES = ["dfx_k_table1.hip", "dfx_k_table2.hip", "dfx_k_table3.hip", "dfx_k_table4.hip", "dfx_k_table8.hip", "dfx_k_core.hip",
-           "dfx_k_reduce.hip", "dfx_k_partition.hip", "dfx_k_partition_v0.hip", "dfx_k_partition_v1.hip", "dfx_k_partition_v2.hip",
-           "dfx_k_partition_v3.hip", "dfx_k_partition_v4.hip", "dfx_k_partition_v5.hip", "dfx_k_partition_v6.hip", "dfx_k_partition_v7.hip", "dfx_k_partition_v8.hip",
-           "dfx_k_partition_v9.hip", "dfx_k_partition_v10.hip", "dfx_k_partition_v11.hip", "dfx_k_partition_v12.hip",
-           "dfx_k_partition_v13.hip", "dfx_k_partition_v14.hip", "dfx_k_partition_v15.hip", "dfx_k_partition_v16.hip",
-           "dfx_k_partition_v17.hip", "dfx_k_partition_v18.hip", "dfx_k_partition_v19.hip", "dfx_k_partition_v20.hip",
-           "dfx_k_partition_v21.hip", "dfx_k_partition_v22.hip", "dfx_k_partition_v23.hip", "dfx_k_partition_v24.hip", "dfx_k_partition_v25.hip", "dfx_k_partition_v26.hip", "dfx_k_partition_v29.hip", "dfx_k_partition_v30.hip",
+           "dfx_k_reduce.hip", "dfx_k_partition.hip"] + [f"dfx_k_partition_{u}.hip" for u in _pass1_units()] + [
            "dfx_k_fewgroup.hip", "dfx_k_distinct1.hip", "dfx_k_distinct2.hip", "dfx_k_distinct3.hip", "dfx_k_distinct4.hip",
            "dfx_k_distinct8.hip", "dfx_k_csv.hip", "dfx_k_sort.hip", "dfx_k_dict.hip", "dfx_k_utf8pred.hip", "dfx_k_utf8agg.hip", "dfx_k_csvwrite.hip", "dfx_host.cpp", "dfx_expr.cpp", "dfx_relation.cpp", "dfx_host_stream.cpp", "dfx_export.cpp",
            "dfx_filter.cpp", "dfx_project.cpp", "dfx_aggregate.cpp", "dfx_aggregate_strategy.cpp",
@@ -33,7 +36,7 @@ SOURCES = ["dfx_k_table1.hip", "dfx_k_table2.hip", "dfx_k_table3.hip", "dfx_k_ta
            "dfx_table.cpp", "dfx_csv.cpp", "dfx_sort.cpp", "dfx_comm.cpp", "dfx_exchange.cpp", "dfx_distinct.cpp", "dfx_distinct_sets.cpp", "dfx_distinct_emit.cpp",
            "dfx_csv_write.cpp"]
 HEADERS = ["dfx_device.hpp", "dfx_sigs.hpp", "dfx_numparse.hpp", "dfx_utf8_match.hpp", "dfx_pow5_table.hpp", "dfx_numfmt.hpp", "dfx_pow10_table.hpp", "dfx_csvwrite.hpp", "dfx_csv_walk.hpp", "dfx_kernels.hpp", "dfx_kernels_inl.hpp", "dfx_k_table_inl.hpp", "dfx_k_partition_inl.hpp", "dfx_k_partition_ws_inl.hpp", "dfx_k_distinct_inl.hpp", "dfx_launch.hpp",
-           "dfx_host.hpp", "dfx_key_shadow.hpp", "dfx_relation.hpp", "dfx_utf8_dict.hpp", "dfx_exchange_plan.hpp", "dfx_comm.hpp", "dfx_aggregate_impl.hpp", "dfx_distinct_impl.hpp", "../../include/dfx.h"]
+           "dfx_host.hpp", "dfx_pass1_units.hpp", "dfx_key_shadow.hpp", "dfx_relation.hpp", "dfx_utf8_dict.hpp", "dfx_exchange_plan.hpp", "dfx_comm.hpp", "dfx_aggregate_impl.hpp", "dfx_distinct_impl.hpp", "../../include/dfx.h"]
 
 # -ffp-contract=off : the reference never fuses a*b+c; projections must be bit-exact
 # -munsafe-fp-atomics: hardware global_atomic_add_f64 / ds_add_f64 instead of CAS loops

@@ -1,6 +1,6 @@
 // dfx_k_partition.hip -- partitioned GROUP BY: the pass-1 dispatcher, pass 2 (k_partition_agg) and the sizing helpers.
 // The pass-1 kernels and the description of the strategy are in dfx_k_partition_inl.hpp; their instantiations are in
-// dfx_k_partition_v0.hip ... _v7.hip.
+// dfx_k_partition_<unit>.hip, one file per unit of dfx_pass1_units.hpp.
 #define DFX_PARTITION_MAIN_TU
 #include "dfx_k_partition_ws_inl.hpp"
 
@@ -776,137 +776,151 @@ uint32_t partition_sort_capacity(uint32_t n_words, uint32_t n_parts, uint32_t bl
   return (uint32_t)cap;
 }
 
-// pass-1 variants (dfx_k_partition_v*.hip)
-void launch_partition_variant0(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant1(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant2(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant3(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant4(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant5(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant6(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant7(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant8(DFX_PARTITION_VARIANT_ARGS);
-void launch_partition_variant9(DFX_PARTITION_VARIANT_ARGS);   // PlanPolicy, <= 2 columns, 8-byte null-free
-void launch_partition_variant10(DFX_PARTITION_VARIANT_ARGS);  // ... 4-byte columns AND validity bitmaps
-void launch_partition_variant11(DFX_PARTITION_VARIANT_ARGS);  // PlanPolicy, <= 4 columns, 8-byte null-free
-void launch_partition_variant12(DFX_PARTITION_VARIANT_ARGS);  // ... 4-byte columns AND validity bitmaps
-void launch_partition_variant13(DFX_PARTITION_VARIANT_ARGS);  // <= 2 columns, 4-byte columns (no bitmap in the batch)
-void launch_partition_variant14(DFX_PARTITION_VARIANT_ARGS);  // <= 2 columns, validity bitmaps (8-byte columns)
-void launch_partition_variant15(DFX_PARTITION_VARIANT_ARGS);  // <= 4 columns, 4-byte columns
-void launch_partition_variant16(DFX_PARTITION_VARIANT_ARGS);  // <= 4 columns, validity bitmaps
-void launch_partition_variant17(DFX_PARTITION_VARIANT_ARGS);  // <= 2 columns, a 4-byte KEY (the only 4-byte column)
-void launch_partition_variant18(DFX_PARTITION_VARIANT_ARGS);  // <= 2 columns, a 4-byte key + validity bitmaps
-void launch_partition_variant19(DFX_PARTITION_VARIANT_ARGS);  // <= 4 columns, a 4-byte key
-void launch_partition_variant20(DFX_PARTITION_VARIANT_ARGS);  // <= 4 columns, a 4-byte key + validity bitmaps
-void launch_partition_variant21(DFX_PARTITION_VARIANT_ARGS);  // 3 columns
-void launch_partition_variant22(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, 4-byte columns
-void launch_partition_variant23(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, validity bitmaps
-void launch_partition_variant24(DFX_PARTITION_VARIANT_ARGS);  // 3 columns, both
-void launch_partition_variant25(DFX_PARTITION_VARIANT_ARGS);  // the headline's signature over the key column's Int32 shadow (two keys per lane)
-void launch_partition_variant26(DFX_PARTITION_VARIANT_ARGS);  // ... key + SUM without a predicate
-void launch_partition_variant29(DFX_PARTITION_VARIANT_ARGS);  // the pair scan, 3 columns, a 4-byte key (one 4-byte load per lane: three row groups per trip have no pairs)
-void launch_partition_variant30(DFX_PARTITION_VARIANT_ARGS);  // ... 4 columns
+// the pass-1 units (dfx_pass1_units.hpp; dfx_k_partition_<unit>.hip defines launch_pass1_<unit>)
+#define X(name) void launch_pass1_##name(DFX_PASS1_ARGS);
+DFX_PASS1_UNITS(X)
+#undef X
+typedef void (*Pass1Launch)(DFX_PASS1_ARGS);
+#define X(name) launch_pass1_##name,
+static const Pass1Launch kPass1Launch[kPass1Units] = {DFX_PASS1_UNITS(X)};
+#undef X
 
-// The Int32 shadow of the key column (PTF_KEY4): which compile-time signature reads this program's key as 4-byte words, two per lane?
-// P, fast: the program as the operator bound it (the key an 8-byte integer column).  0: none -- the scan plan may still bind the
-// shadow (partition_key_shadow_supported).  (DFX_PARTITION_VARIANT_WS_ONLY)
-static int partition_key_shadow_variant(const DevProgram& P, const DevFastPlan& fast, const DevTable& T, const DevPartition& PT) {
-  if (!(PT.flags & PTF_WS) || (PT.flags & PTF_PAIR) || !(PT.flags & PTF_NARROW) || (fast.plan_mode & 3) == 2 || T.kw != 1) return 0;
-  const bool shared = (PT.flags & PTF_SHARED) != 0;
-  const uint8_t raw_kind0[1] = {SigKeySumPred2F64::acc(0)}, raw_kind1[1] = {SigKeySum::acc(0)}, raw_xf[1] = {VT_RAW};
-  if (shared ? sig_matches<SigKeySumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf) : sig_matches<SigKeySumPred2F64>(P, fast, 1, T.na, T.acc_kind, T.val_xform))
-    return 25;
-  if (shared ? sig_matches<SigKeySum>(P, fast, 1, 1, raw_kind1, raw_xf) : sig_matches<SigKeySum>(P, fast, 1, T.na, T.acc_kind, T.val_xform)) return 26;
-  return 0;
+// What select_pass1 decides: the unit that takes a launch and what it is launched with.
+struct Pass1Choice {
+  Pass1Unit unit = Pass1Unit::none;  // none: no pass-1 kernel takes this launch
+  bool bound = false;                // the scan plan bound the batch: the launch takes fp / cp in place of the caller's fast plan and columns
+  DevFastPlan fp;
+  DevColumns cp;
+  DevPartition PT;       // the launch's: the pair scan's slot and transform filled in, PTF_WS stripped for fast_* / interp_*
+  size_t lds_bytes = 0;  // of that PT
+};
+
+// The compile-time signature this program matches, as its static_* unit.  raw (PTF_SHARED): pass 1 routes the aggregates' common
+// RAW operand -- the shape of a one-aggregate query whose operand is that column (what the accumulators do with it is pass 2's
+// business).
+static Pass1Unit signature_unit(const DevProgram& P, const DevFastPlan& fast, const DevTable& T, bool raw) {
+  static_assert(SigKeySumPred2F64::acc(0) == ACC_ADD_F64 && SigKeySum::acc(0) == ACC_ADD_F64 && SigKeyAffSumPred2F64::acc(0) == ACC_ADD_F64 &&
+                    SigKeySumPred2F64::xf(0) == VT_RAW && SigKeySum::xf(0) == VT_RAW && SigKeyAffSumPred2F64::xf(0) == VT_RAW,
+                "the one-aggregate signatures add the raw operand");
+  const uint8_t raw_kind[1] = {ACC_ADD_F64}, raw_xf[1] = {VT_RAW};
+  const int na = raw ? 1 : T.na;
+  const uint8_t* kind = raw ? raw_kind : T.acc_kind;
+  const uint8_t* xf = raw ? raw_xf : T.val_xform;
+  if (sig_matches<SigKeySumPred2F64>(P, fast, 1, na, kind, xf)) return Pass1Unit::static_key_sum_pred2;
+  if (sig_matches<SigKeySum>(P, fast, 1, na, kind, xf)) return Pass1Unit::static_key_sum;
+  if (sig_matches<SigKeyAffSumPred2F64>(P, fast, 1, na, kind, xf)) return Pass1Unit::static_key_aff_sum_pred2;
+  return Pass1Unit::none;
 }
 
 // The scan plan (DevScanPlan): run-time shapes as data.  Which binding a launch needs follows from the kernel flavour that
 // will run: the one-value flavours (narrow rows, the wave-specialised kernel) find the key in slot 0 and the routed value in
-// slot 1 (PlanPolicy1), the others look their slots up.
-// dry: bind only -- would a launch go through?  (host only, no launch)
-static bool launch_partition_plan(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,
-                                  const DevTable& T, const DevPartition& PT, const DevRows& spill, int64_t n, size_t lds_bytes,
-                                  hipStream_t s, bool dry = false) {
+// slot 1 (PlanPolicy1), the others look their slots up.  false: the plan does not take this launch (c->unit stays none).
+static bool select_plan_unit(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT, Pass1Choice* c) {
   const bool shared = (PT.flags & PTF_SHARED) != 0;
   const bool pair = (PT.flags & PTF_PAIR) != 0;  // two operands per routed row: the multi-value binding (slot look-ups) in the wave-specialised kernel
+  const bool key4 = (PT.flags & PTF_KEY4) != 0;
   const bool one_value = !pair && ((PT.flags & PTF_WS) || ((PT.mode & 15u) == 2 && (PT.flags & PTF_NARROW)));
   if (one_value && !shared && T.na != 1) return false;
   if (pair && (T.na < 2 || T.kw != 1 || !(PT.flags & PTF_WS))) return false;
   const uint8_t raw_xf[kMaxAggs] = {VT_RAW};
-  DevFastPlan fp;
-  DevColumns cp;
   // (a pair scan whose key is the only 4-byte column -- the Int32 shadow -- has kernels of its own: asked for under PTF_KEY4 alone)
-  if (!bind_scan_plan(P, fast, C, 1, shared ? 1 : T.na, shared ? raw_xf : T.val_xform, one_value, &fp, &cp, pair && (PT.flags & PTF_KEY4))) return false;
-  typedef void (*Variant)(DFX_PARTITION_VARIANT_ARGS);
-  // [> 2 columns][DevScanPlan::gen: bit 0 4-byte columns, bit 1 validity bitmaps, bit 2 (instead of bit 0) a 4-byte key only]
-  static const Variant by_need[3][8] = {
-      {launch_partition_variant9, launch_partition_variant13, launch_partition_variant14, launch_partition_variant10,
-       launch_partition_variant17, launch_partition_variant13, launch_partition_variant18, launch_partition_variant10},
-      {launch_partition_variant21, launch_partition_variant22, launch_partition_variant23, launch_partition_variant24,
-       launch_partition_variant19, launch_partition_variant22, launch_partition_variant20, launch_partition_variant24},
-      {launch_partition_variant11, launch_partition_variant15, launch_partition_variant16, launch_partition_variant12,
-       launch_partition_variant19, launch_partition_variant15, launch_partition_variant20, launch_partition_variant12}};
-  if (!one_value && !pair && (fp.scan.gen & 4)) return false;  // (cannot happen: bind_scan_plan gives bit 2 to fixed-slot bindings and to the pair scan over a shadow)
-  // Over a shadow only the forms that load the key as a 4-byte word.  A second 4-byte slot -- COUNT(k) GROUP BY k binds the key
-  // twice -- would take the generic 4-byte-column form (the aligned 8 bytes that hold the element, a lane select), which the pair
-  // kernels ran at half the speed of the 8-byte key: such launches keep the 8-byte column.
-  if ((PT.flags & PTF_KEY4) && (fp.scan.gen & 7) != 4) return false;  // (pair scan: 10.2 ms against 5.5 ms of pass 1 per 10^9 rows)
-  if (pair && fp.scan.n_cols != 3 && fp.scan.n_cols != 4) return false;  // (the pair kernels: key + two operand columns, and one more predicate column -- variants 21-24, 11 / 15 / 16 / 12)
-  DevPartition PTp = PT;
+  if (!bind_scan_plan(P, fast, C, 1, shared ? 1 : T.na, shared ? raw_xf : T.val_xform, one_value, &c->fp, &c->cp, pair && key4)) return false;
+  const Pass1Unit unit = plan_unit(c->fp.scan.n_cols, c->fp.scan.gen, pair, one_value, key4);
+  if (unit == Pass1Unit::none) return false;
+  c->unit = unit;
+  c->bound = true;
   if (pair) {  // operand 1: the plan slot and the transform of its first accumulator
     const uint32_t a1 = PT.pair_arg1 < (uint32_t)kMaxAggs ? PT.pair_arg1 : 1u;
-    PTp.pair_slot1 = fp.scan.argslot[a1];
-    PTp.pair_xf1 = T.val_xform[a1];
+    c->PT.pair_slot1 = c->fp.scan.argslot[a1];
+    c->PT.pair_xf1 = T.val_xform[a1];
   }
-  if (dry) return true;
-  if (pair && (fp.scan.gen & 4)) {
-    (fp.scan.n_cols == 3 ? launch_partition_variant29 : launch_partition_variant30)(P, fp, cp, plan, T, PTp, spill, n, lds_bytes, s);
-    return true;
-  }
-  by_need[fp.scan.n_cols <= 2 ? 0 : fp.scan.n_cols == 3 ? 1 : 2][fp.scan.gen & 7](P, fp, cp, plan, T, PTp, spill, n, lds_bytes, s);
   return true;
 }
 
-// PTF_PAIR: can THIS bound batch go through the pair kernels?  (the plan binds it, three plan columns; host only, no launch)
+// Which pass-1 unit takes this launch, and with what?  Host only, no launch: launch_partition runs the answer, the
+// partition_*_supported queries below predict it from the same code.  P, fast, C: the batch as the launch binds it -- under
+// PTF_KEY4 the key column is its Int32 shadow (T_U32).
+static Pass1Choice select_pass1(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT) {
+  Pass1Choice c;
+  c.PT = PT;
+  c.lds_bytes = partition_stage_bytes(PT);
+  const bool shared = (PT.flags & PTF_SHARED) != 0;
+  const bool plan_first = (fast.plan_mode & 3) == 2;  // (A/B: scan.plan = 2)
+  if (PT.flags & PTF_KEY4) {
+    // The two signatures that have a two-keys-per-lane kernel (StaticKey4Policy: the wave-specialised kernel alone) describe the
+    // 8-byte binding; whatever else the scan plan binds with the key as an unsigned 4-byte column: its one-value kernels
+    // (plan_c2_g4, plan_c4_g4) and the pair kernels (pair_key4_*), one 4-byte load per lane.
+    if ((PT.flags & PTF_WS) && !(PT.flags & PTF_PAIR) && (PT.flags & PTF_NARROW) && !plan_first && T.kw == 1) {
+      DevProgram P8 = P;
+      if (fast.valid && fast.keycol[0] < kMaxCols) P8.col_dtype[fast.keycol[0]] = T_I64;
+      const Pass1Unit sig = signature_unit(P8, fast, T, shared);
+      if (sig == Pass1Unit::static_key_sum_pred2) c.unit = Pass1Unit::key4_static_key_sum_pred2;
+      if (sig == Pass1Unit::static_key_sum) c.unit = Pass1Unit::key4_static_key_sum;
+      if (c.unit != Pass1Unit::none) return c;
+    }
+    select_plan_unit(P, fast, C, T, PT, &c);
+    return c;
+  }
+  if (PT.flags & PTF_PAIR) {  // (the host asked partition_pair_supported first: a batch the plan cannot bind is its error to handle)
+    select_plan_unit(P, fast, C, T, PT, &c);
+    return c;
+  }
+  if (plan_first && select_plan_unit(P, fast, C, T, PT, &c)) return c;
+  c.unit = signature_unit(P, fast, T, shared);
+  if (c.unit != Pass1Unit::none) return c;
+  // everything else the plan covers: any single MIN / MAX / COUNT / SUM, one to four terms over Int32 ... Float64 columns,
+  // nullable columns -- same kernels, the query is data (the wave-specialised flavour included: its scan loop stays short)
+  if (!plan_first && select_plan_unit(P, fast, C, T, PT, &c)) return c;
+  if (PT.flags & PTF_PLANES) return c;  // (the host asked partition_planes_supported first; the ring kernels below write another geometry)
+  if (fast.plan_mode & 4) return c;     // (the host fused a predicate over nulls counting on a plan)
+  // The wave-specialised flavour pays when the scan loop is short (compile-time signatures).  The run-time decoded shapes and
+  // the interpreter spend several times as many instructions per row group: eight scanner waves cannot keep up, sixteen
+  // symmetric ones can (measured with PTF_WS on every policy: FastPolicy queries -25 %, the interpreter -28 %).  Same regions,
+  // counts and padding either way, so the choice is made per launch.
+  c.PT.flags &= ~PTF_WS;
+  c.lds_bytes = partition_stage_bytes(c.PT);
+  const bool use_fast = fast.valid && !P.has_nulls;
+  c.unit = P.n_cols <= 2 ? (use_fast ? Pass1Unit::fast_c2 : Pass1Unit::interp_c2)
+           : P.n_cols <= 4 ? (use_fast ? Pass1Unit::fast_c4 : Pass1Unit::interp_c4)
+                           : (use_fast ? Pass1Unit::fast_c8 : Pass1Unit::interp_c8);
+  return c;
+}
+
+// PTF_PAIR: can THIS bound batch go through the pair kernels?  (the plan binds it, three or four plan columns)
 bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T) {
   if (!kNarrowLine || T.na < 2 || T.kw != 1) return false;
   if (T.na > 2 && P.has_nulls && fast.np == 0) return false;  // (three and more aggregates: the operands travel raw -- see partition_planes_supported)
-  DevFastPlan fp;
-  DevColumns cp;
-  if (!bind_scan_plan(P, fast, C, 1, T.na, T.val_xform, false, &fp, &cp)) return false;
-  return (fp.scan.n_cols == 3 || fp.scan.n_cols == 4) && !(fp.scan.gen & 4);
+  DevPartition PTq = {};
+  PTq.flags = PTF_WS | PTF_PAIR;
+  Pass1Choice c;
+  return select_plan_unit(P, fast, C, T, PTq, &c) && !(c.fp.scan.gen & 4);
 }
 
 // PTF_KEY4: does a pass-1 kernel read this program's key from 4-byte words?  P, fast, C: the batch as the operator bound it, the
-// key (slot ks) an 8-byte integer column without nulls; PT: the launch's flags.  The two compile-time signatures (two keys per
-// lane), or whatever the scan plan binds with the key as an unsigned 4-byte column: its one-value kernels (variants 17 and 19) and
-// the pair kernels (29 and 30), one 4-byte load per lane.  The plan
-// refuses what it cannot widen -- an aggregate over the key itself, a product --: those launches keep the 8-byte column.
+// key (slot ks) an 8-byte integer column without nulls; PT: the launch's flags.  The plan refuses what it cannot widen -- an
+// aggregate over the key itself, a product --: those launches keep the 8-byte column.
 bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT) {
   if (!(PT.flags & PTF_WS) || T.kw != 1 || !fast.valid) return false;
-  if (partition_key_shadow_variant(P, fast, T, PT)) return true;
   const int ks = fast.keycol[0];
   if (ks >= kMaxCols) return false;
   DevProgram P4 = P;
   P4.col_dtype[ks] = T_U32;  // (C's own 8-byte aligned base stands in for the shadow's)
   DevPartition PT4 = PT;
   PT4.flags |= PTF_KEY4;
-  return launch_partition_plan(P4, fast, C, DevAggPlan{}, T, PT4, DevRows{}, 0, 0, nullptr, true);
+  return select_pass1(P4, fast, C, T, PT4).unit != Pass1Unit::none;
 }
 
 // PTF_PLANES: does THIS bound batch take the wave-specialised one-value pass 1 with the aggregates' common raw operand?
-// (a compile-time signature of the raw shape, or the scan plan's fixed-slot binding; host only, no launch)
+// (a compile-time signature of the raw shape, or the scan plan's fixed-slot binding)
 bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T) {
   // (nulls: a raw operand carries no validity.  Under an absorbed predicate nobody asks for it -- every surviving slot is valid,
   // filter.rs:83-92, DevScanPlan::count_valid --; without one COUNT would)
   if (!kNarrowLine || T.na < 2 || T.na > kMaxAggs || T.kw != 1 || (P.has_nulls && fast.np == 0)) return false;
-  const uint8_t raw_kind0[1] = {SigKeySumPred2F64::acc(0)}, raw_kind1[1] = {SigKeySum::acc(0)}, raw_xf[kMaxAggs] = {VT_RAW};
-  if ((fast.plan_mode & 3) != 2 && (sig_matches<SigKeySumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf) || sig_matches<SigKeySum>(P, fast, 1, 1, raw_kind1, raw_xf) ||
-                                    sig_matches<SigKeyAffSumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf)))
-    return true;
-  DevFastPlan fp;
-  DevColumns cp;
-  return bind_scan_plan(P, fast, C, 1, 1, raw_xf, true, &fp, &cp);
+  if ((fast.plan_mode & 3) != 2 && signature_unit(P, fast, T, true) != Pass1Unit::none) return true;
+  DevPartition PTq = {};
+  PTq.flags = PTF_WS | PTF_SHARED;
+  Pass1Choice c;
+  return select_plan_unit(P, fast, C, T, PTq, &c);
 }
 
 hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,
@@ -920,52 +934,9 @@ hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const 
   if ((PT.mode & 15u) == 1 && (lds_bytes > 160 * 1024 || PT.stage_rows == 0 || PT.stage_rows > (uint32_t)kSortMaxCap ||
                        PT.n_parts > 4096 || (PT.block != 512 && PT.block != 1024)))
     return hipErrorInvalidValue;
-  // PTF_SHARED: pass 1 routes the aggregates' common RAW operand -- the shape of a one-aggregate query whose operand is
-  // that column (what the accumulators do with it is pass 2's business)
-  const bool shared = (PT.flags & PTF_SHARED) != 0;
-  const uint8_t raw_kind0[1] = {SigKeySumPred2F64::acc(0)}, raw_kind1[1] = {SigKeySum::acc(0)}, raw_xf[1] = {VT_RAW};
-  static_assert(SigKeySumPred2F64::xf(0) == VT_RAW && SigKeySum::xf(0) == VT_RAW, "the one-aggregate signatures route the raw operand");
-  if (PT.flags & PTF_KEY4) {  // (the host asked partition_key_shadow_variant first, with the 8-byte binding; C.c[key] is the shadow)
-    DevProgram P8 = P;
-    if (fast.valid && fast.keycol[0] < kMaxCols) P8.col_dtype[fast.keycol[0]] = T_I64;
-    switch (partition_key_shadow_variant(P8, fast, T, PT)) {
-      case 25: launch_partition_variant25(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); return hipGetLastError();
-      case 26: launch_partition_variant26(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); return hipGetLastError();
-      default: break;
-    }
-    return launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s) ? hipGetLastError() : hipErrorNotSupported;  // (the key an unsigned 4-byte column)
-  }
-  if (PT.flags & PTF_PAIR)  // (the host asked partition_pair_supported first: a batch the plan cannot bind is its error to handle)
-    return launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s) ? hipGetLastError() : hipErrorNotSupported;
-  if ((fast.plan_mode & 3) == 2 && launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s)) return hipGetLastError();  // (A/B: scan.plan = 2)
-  if (shared ? sig_matches<SigKeySumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf) : sig_matches<SigKeySumPred2F64>(P, fast, 1, T.na, T.acc_kind, T.val_xform)) {
-    launch_partition_variant0(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
-    return hipGetLastError();
-  }
-  if (shared ? sig_matches<SigKeySum>(P, fast, 1, 1, raw_kind1, raw_xf) : sig_matches<SigKeySum>(P, fast, 1, T.na, T.acc_kind, T.val_xform)) {
-    launch_partition_variant1(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
-    return hipGetLastError();
-  }
-  if (shared ? sig_matches<SigKeyAffSumPred2F64>(P, fast, 1, 1, raw_kind0, raw_xf) : sig_matches<SigKeyAffSumPred2F64>(P, fast, 1, T.na, T.acc_kind, T.val_xform)) {
-    launch_partition_variant8(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
-    return hipGetLastError();
-  }
-  // everything else the plan covers: any single MIN / MAX / COUNT / SUM, one to four terms over Int32 ... Float64 columns,
-  // nullable columns -- same kernels, the query is data (the wave-specialised flavour included: its scan loop stays short)
-  if (launch_partition_plan(P, fast, C, plan, T, PT, spill, n, lds_bytes, s)) return hipGetLastError();
-  if (PT.flags & PTF_PLANES) return hipErrorNotSupported;  // (the host asked partition_planes_supported first; the ring kernels below write another geometry)
-  if (fast.plan_mode & 4) return hipErrorNotSupported;  // (the host fused a predicate over nulls counting on a plan)
-  const bool use_fast = fast.valid && !P.has_nulls;
-  // The wave-specialised flavour pays when the scan loop is short (compile-time signatures).  The run-time decoded shapes and
-  // the interpreter spend several times as many instructions per row group: eight scanner waves cannot keep up, sixteen
-  // symmetric ones can (measured with PTF_WS on every policy: FastPolicy queries -25 %, the interpreter -28 %).  Same regions,
-  // counts and padding either way, so the choice is made per launch.
-  DevPartition PTg = PT;
-  PTg.flags &= ~PTF_WS;
-  const size_t lds_g = partition_stage_bytes(PTg);
-  if (P.n_cols <= 2) { if (use_fast) launch_partition_variant2(P, fast, C, plan, T, PTg, spill, n, lds_g, s); else launch_partition_variant3(P, fast, C, plan, T, PTg, spill, n, lds_g, s); }
-  else if (P.n_cols <= 4) { if (use_fast) launch_partition_variant4(P, fast, C, plan, T, PTg, spill, n, lds_g, s); else launch_partition_variant5(P, fast, C, plan, T, PTg, spill, n, lds_g, s); }
-  else { if (use_fast) launch_partition_variant6(P, fast, C, plan, T, PTg, spill, n, lds_g, s); else launch_partition_variant7(P, fast, C, plan, T, PTg, spill, n, lds_g, s); }
+  const Pass1Choice c = select_pass1(P, fast, C, T, PT);
+  if (c.unit == Pass1Unit::none) return hipErrorNotSupported;
+  kPass1Launch[(int)c.unit](P, c.bound ? c.fp : fast, c.bound ? c.cp : C, plan, T, c.PT, spill, n, c.lds_bytes, s);
   return hipGetLastError();
 }
 

@@ -17,13 +17,14 @@
 // Rows that do not fit (a region overflows: heavy skew; a block is full) go to the ordinary spill
 // list and are merged by the global-atomic path, so the strategy is correct for any distribution.
 //
-// Translation units: the pass-1 kernels below are templates over the row-source policy; every (policy, write-combining
-// policy) pair is instantiated in its own file (dfx_k_partition_v0.hip ... _v7.hip, one DFX_PARTITION_VARIANT line each)
-// so that they compile in parallel; dfx_k_partition.hip holds the dispatcher (launch_partition), pass 2 and the sizing
-// helpers.
+// Translation units: the pass-1 kernels below are templates over the row-source policy; every unit of the list in
+// dfx_pass1_units.hpp instantiates its policies in its own file (dfx_k_partition_<unit>.hip, one DFX_PASS1_UNIT line each:
+// dfx_k_partition_ws_inl.hpp) so that they compile in parallel; dfx_k_partition.hip holds the dispatcher (select_pass1,
+// launch_partition), pass 2 and the sizing helpers.
 #pragma once
 #include "dfx_kernels_inl.hpp"
 #include "dfx_launch.hpp"
+#include "dfx_pass1_units.hpp"
 
 namespace dfx {
 
@@ -1142,13 +1143,9 @@ void launch_partition_pol(const DevProgram& P, const DevFastPlan& fast, const De
     hipLaunchKernelGGL((k_partition_sorted<POLS, 1024>), dim3(grid), dim3(1024), lds_bytes, s, P, fast, C, plan, T, PT, spill, n);
 }
 
-// one pass-1 variant = one translation unit
-#define DFX_PARTITION_VARIANT_ARGS                                                                                         \
+// what every unit's launcher takes (launch_pass1_<unit>: DFX_PASS1_UNIT, dfx_k_partition_ws_inl.hpp)
+#define DFX_PASS1_ARGS                                                                                                     \
   const DevProgram &P, const DevFastPlan &fast, const DevColumns &C, const DevAggPlan &plan, const DevTable &T,            \
       const DevPartition &PT, const DevRows &spill, int64_t n, size_t lds_bytes, hipStream_t s
-#define DFX_PARTITION_VARIANT(ID, POL, POLS, ...)                                                                          \
-  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
-    launch_partition_pol<POL, POLS, ##__VA_ARGS__>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                      \
-  }
 
 }  // namespace dfx

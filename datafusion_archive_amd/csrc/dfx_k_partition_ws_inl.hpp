@@ -354,41 +354,81 @@ void launch_partition_ws(const DevProgram& P, const DevFastPlan& fast, const Dev
 #undef DFX_WS_LAUNCH
 }
 
-// one pass-1 variant = one translation unit: the ring / sorted / direct kernels of the policy plus its wave-specialised kernel
-// (POLW: the one-value policy of the wave-specialised kernel -- the scanners can afford more row groups per trip than the
-// ring kernels, whose routing state competes for the same 128 registers)
-// POLD: the one-value policy of the DENSE wave-specialised split (four scanners: eight row groups per trip)
-#define DFX_PARTITION_VARIANT_WS(ID, POL, POLS, POLN, POLW, POLD)                                                          \
-  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
-    if (PT.flags & PTF_WS)                                                                                                 \
-      launch_partition_ws<POLW, POLD>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                                    \
-    else                                                                                                                   \
-      launch_partition_pol<POL, POLS, POLN>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                              \
-  }
+// One pass-1 unit (dfx_pass1_units.hpp) = one translation unit = the kernels of one set of row-source policies.  A slot the unit
+// does not have is void: nothing of it is instantiated, and the launcher below skips it.
+//   RING    the direct / ring kernels;  WC: the write-combining (sorted) and the wide ring kernels;  NARROW: the narrow-row rings
+//           (one routed value)
+//   WS      the one-value policy of the wave-specialised kernel -- the scanners can afford more row groups per trip than the ring
+//           kernels, whose routing state competes for the same 128 registers;  DENSE: of its dense split (four scanners)
+//   PAIR    the PAIR flavour (PTF_PAIR), for the policies that can evaluate two arguments (slot look-ups, PlanPolicyN): always
+//           eight scanners + eight routers (twelve routers' queues with two operand planes do not fit the LDS), the run-time
+//           comparison form
+template <typename RING, typename WC, typename NARROW, typename WS = void, typename DENSE = void, typename PAIR = void>
+struct Pass1Policies {
+  typedef RING ring;
+  typedef WC wc;
+  typedef NARROW narrow;
+  typedef WS ws;
+  typedef DENSE dense;
+  typedef PAIR pair;
+};
 
-
-// a policy that only the wave-specialised kernel knows (StaticKey4Policy): the host asks for it under PTF_WS alone
-#define DFX_PARTITION_VARIANT_WS_ONLY(ID, POLW, POLD)                                                                      \
-  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
-    launch_partition_ws<POLW, POLD>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                                      \
+// A unit with no other kernels launches its wave-specialised (or pair) kernel whatever the flags say: the host asks for
+// key4_* under PTF_WS alone and for pair_key4_* under PTF_WS | PTF_PAIR alone (select_pass1).
+template <typename U>
+void launch_pass1(DFX_PASS1_ARGS) {
+  constexpr bool has_ring = !std::is_void<typename U::ring>::value, has_ws = !std::is_void<typename U::ws>::value;
+  if constexpr (!std::is_void<typename U::pair>::value) {
+    if (!has_ws || ((PT.flags & PTF_WS) && (PT.flags & PTF_PAIR))) {
+      hipLaunchKernelGGL((k_partition_ws<typename U::pair, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n);
+      return;
+    }
   }
-
-// ... the PAIR flavour alone (the pair scan over a 4-byte key: PlanPolicyN with GENK = 4)
-#define DFX_PARTITION_VARIANT_WS_PAIR_ONLY(ID, POLP)                                                                       \
-  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
-    hipLaunchKernelGGL((k_partition_ws<POLP, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n); \
+  if constexpr (has_ws) {
+    if (!has_ring || (PT.flags & PTF_WS)) {
+      launch_partition_ws<typename U::ws, typename U::dense>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
+      return;
+    }
   }
+  if constexpr (has_ring) launch_partition_pol<typename U::ring, typename U::wc, typename U::narrow>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
+}
+#define DFX_PASS1_UNIT(NAME, ...) /* at file scope: a unit's file is this line */ \
+  namespace dfx { void launch_pass1_##NAME(DFX_PASS1_ARGS) { launch_pass1<__VA_ARGS__>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); } }
 
-// ... and, for the policies that can evaluate two arguments (POLP: slot look-ups, PlanPolicyN), the PAIR flavour (PTF_PAIR): always
-// eight scanners + eight routers (twelve routers' queues with two operand planes do not fit the LDS), the run-time comparison form
-#define DFX_PARTITION_VARIANT_WS_PAIR(ID, POL, POLS, POLN, POLW, POLD, POLP)                                               \
-  void launch_partition_variant##ID(DFX_PARTITION_VARIANT_ARGS) {                                                          \
-    if ((PT.flags & PTF_WS) && (PT.flags & PTF_PAIR))                                                                      \
-      hipLaunchKernelGGL((k_partition_ws<POLP, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n); \
-    else if (PT.flags & PTF_WS)                                                                                            \
-      launch_partition_ws<POLW, POLD>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                                    \
-    else                                                                                                                   \
-      launch_partition_pol<POL, POLS, POLN>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);                              \
-  }
+// a compile-time signature: four row groups per trip, eight in the dense split;  ... over the key's Int32 shadow (StaticKey4Policy:
+// only the wave-specialised kernel knows it)
+template <typename SIG>
+using StaticUnit = Pass1Policies<StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 8, SIG>>;
+template <typename SIG>
+using StaticKey4Unit = Pass1Policies<void, void, void, StaticKey4Policy<4, SIG>, StaticKey4Policy<8, SIG>>;
+
+// The scan plan's units (PlanPolicy: range tests on value images, plan words in vector registers): row groups per trip by column
+// class (NC = 2: <= 2 columns; 3: exactly 3 -- key, routed value, one more predicate column, e.g. SUM(w) WHERE v ... GROUP BY k, or
+// the second scan of SUM(v), MIN(w) --; 4: <= 4) and GENK.  The pair flavour runs the trips of the wave-specialised one.
+struct PlanTrips {
+  int ring, ws, dense;
+};
+constexpr PlanTrips plan_trips(int nc, int genk) {
+  // A 4-byte key and no bitmaps, <= 2 columns: eight row groups per trip in the wave-specialised flavour.  12 bytes per row instead
+  // of 16 leave this kernel below the traffic ceiling the 8-byte kernels sit at, and it is the bytes in flight that bound it
+  // (431 -> 407 us per 2^27-row launch).
+  if (nc == 2 && genk == 4) return {2, 8, 4};
+  return nc == 2 ? PlanTrips{2, 4, 4} : nc == 3 ? PlanTrips{1, 3, 3} : PlanTrips{1, 2, 2};
+}
+template <int NC, int GENK>
+struct PlanUnit {
+  static constexpr PlanTrips t = plan_trips(NC, GENK);
+  static constexpr bool key4 = (GENK & 4) != 0;  // bit 2 belongs to the one-key, one-value binding: fixed slots in every flavour, no pair
+  typedef PlanPolicy<NC, t.ring, GENK, key4> ring;
+  typedef ring wc;
+  typedef PlanPolicy1<NC, t.ring, GENK> narrow;
+  typedef PlanPolicy1<NC, t.ws, GENK> ws;
+  typedef PlanPolicy1<NC, t.dense, GENK> dense;
+  typedef typename std::conditional<NC >= 3 && !key4, PlanPolicyN<NC, t.ws, GENK>, void>::type pair;  // (+ the PAIR flavour: two aggregates of different operands routed by ONE scan -- PTF_PAIR, dfx_device.hpp)
+};
+// the pair scan over a 4-byte key (GENK = 4: the key in slot 0 is the only 4-byte column -- the Int32 shadow of a resident Int64 key
+// column, read with one 4-byte load per lane; three row groups per trip have no pairs).  Trips as in the 8-byte unit of the same width.
+template <int NC>
+using PairKey4Unit = Pass1Policies<void, void, void, void, void, PlanPolicyN<NC, plan_trips(NC, 4).ws, 4>>;
 
 }  // namespace dfx

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_headline_pass1_kernel_instruction_and_spill_budget():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_meta.py"), "dfx_k_partition_v0"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_meta.py"), "dfx_k_partition_static_key_sum_pred2"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if "SigKeySumPred2F64>, 8, 12, 1>" in ln and "StaticPolicy<2, 4," in ln]
     assert len(line) == 1, r.stdout[-2000:]

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register / spill metadata and the instruction mix of the scan loop of the pass-1 kernels, from the device assembly of the
 translation units as the library builds them (hipcc --cuda-device-only -S with build.py's flags; no GPU needed).
-usage: kernel_meta.py [unit ...]   (default: dfx_k_partition_v0 = compile-time signatures, v9 = scan plan, v17 = scan plan with a 4-byte key)
+usage: kernel_meta.py [unit ...]   (default: dfx_k_partition_static_key_sum_pred2 = compile-time signatures, plan_c2_g0 = scan plan, plan_c2_g4 = scan plan with a 4-byte key;
+the units are listed in csrc/dfx_pass1_units.hpp)
 Prints one line per kernel symbol matching k_partition_ws: SGPRs, spilled SGPRs, VGPRs, spilled VGPRs, scratch bytes, total
 instructions, v_readlane / v_writelane counts (SGPR spill traffic).  profiles/r04_kernel_metadata.txt is its output."""
 import os
@@ -26,7 +27,7 @@ def demangle(names):
 
 def main():
     every = "--all" in sys.argv  # every kernel of the unit, not only k_partition_ws
-    units = [a for a in sys.argv[1:] if not a.startswith("--")] or ["dfx_k_partition_v0", "dfx_k_partition_v9", "dfx_k_partition_v17"]
+    units = [a for a in sys.argv[1:] if not a.startswith("--")] or ["dfx_k_partition_static_key_sum_pred2", "dfx_k_partition_plan_c2_g0", "dfx_k_partition_plan_c2_g4"]
     hipcc = B._hipcc()
     flags = [f for f in B.CXXFLAGS if f != "-fPIC"]
     for u in units:
