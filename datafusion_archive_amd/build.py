@@ -28,7 +28,7 @@ def _pass1_units() -> List[str]:
 
 # kernel translation units first (slowest): they compile in parallel
 SOURCES = ["dfx_k_table1.hip", "dfx_k_table2.hip", "dfx_k_table3.hip", "dfx_k_table4.hip", "dfx_k_table8.hip", "dfx_k_core.hip",
-           "dfx_k_reduce.hip", "dfx_k_partition.hip"] + [f"dfx_k_partition_{u}.hip" for u in _pass1_units()] + [
+           "dfx_k_reduce.hip", "dfx_k_pass2.hip", "dfx_k_partition.hip"] + [f"dfx_k_partition_{u}.hip" for u in _pass1_units()] + [
            "dfx_k_fewgroup.hip", "dfx_k_distinct1.hip", "dfx_k_distinct2.hip", "dfx_k_distinct3.hip", "dfx_k_distinct4.hip",
            "dfx_k_distinct8.hip", "dfx_k_csv.hip", "dfx_k_sort.hip", "dfx_k_dict.hip", "dfx_k_utf8pred.hip", "dfx_k_utf8agg.hip", "dfx_k_csvwrite.hip", "dfx_host.cpp", "dfx_expr.cpp", "dfx_relation.cpp", "dfx_host_stream.cpp", "dfx_export.cpp",
            "dfx_filter.cpp", "dfx_project.cpp", "dfx_aggregate.cpp", "dfx_aggregate_strategy.cpp",
@@ -36,13 +36,13 @@ SOURCES = ["dfx_k_table1.hip", "dfx_k_table2.hip", "dfx_k_table3.hip", "dfx_k_ta
            "dfx_table.cpp", "dfx_csv.cpp", "dfx_sort.cpp", "dfx_comm.cpp", "dfx_exchange.cpp", "dfx_distinct.cpp", "dfx_distinct_sets.cpp", "dfx_distinct_emit.cpp",
            "dfx_csv_write.cpp"]
 HEADERS = ["dfx_device.hpp", "dfx_sigs.hpp", "dfx_numparse.hpp", "dfx_utf8_match.hpp", "dfx_pow5_table.hpp", "dfx_numfmt.hpp", "dfx_pow10_table.hpp", "dfx_csvwrite.hpp", "dfx_csv_walk.hpp", "dfx_kernels.hpp", "dfx_kernels_inl.hpp", "dfx_k_table_inl.hpp", "dfx_k_partition_inl.hpp", "dfx_k_partition_ws_inl.hpp", "dfx_k_distinct_inl.hpp", "dfx_launch.hpp",
-           "dfx_host.hpp", "dfx_pass1_units.hpp", "dfx_key_shadow.hpp", "dfx_relation.hpp", "dfx_utf8_dict.hpp", "dfx_exchange_plan.hpp", "dfx_comm.hpp", "dfx_aggregate_impl.hpp", "dfx_distinct_impl.hpp", "../../include/dfx.h"]
+           "dfx_host.hpp", "dfx_pass1_units.hpp", "dfx_pass2_forms.hpp", "dfx_key_shadow.hpp", "dfx_relation.hpp", "dfx_utf8_dict.hpp", "dfx_exchange_plan.hpp", "dfx_comm.hpp", "dfx_aggregate_impl.hpp", "dfx_distinct_impl.hpp", "../../include/dfx.h"]
 
 # -ffp-contract=off : the reference never fuses a*b+c; projections must be bit-exact
 # -munsafe-fp-atomics: hardware global_atomic_add_f64 / ds_add_f64 instead of CAS loops
 CXXFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
             "-munsafe-fp-atomics", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
-CXXFLAGS += os.environ.get("DFX_EXTRA_CXXFLAGS", "").split()  # debug builds (e.g. -DDFX_PA_TIMING)
+CXXFLAGS += os.environ.get("DFX_EXTRA_CXXFLAGS", "").split()  # debug builds
 
 
 def _hipcc() -> str:
@@ -80,12 +80,12 @@ def _recorded_flags(obj: str) -> str:
 
 
 # ---- build-time guard: hand-scheduled registers of pass 2 ------------------------------------------------------------------
-# k_partition_agg_lean (csrc/dfx_k_partition.hip) issues its row loads by inline assembly into VGPRs v88..v119, which the kernel
+# k_partition_agg_lean (csrc/dfx_k_pass2.hip) issues its row loads by inline assembly into VGPRs v88..v119, which the kernel
 # withholds from the register allocator (amdgpu_num_vgpr(88)).  That is only sound while (a) the code object ALLOCATES those
 # registers (its .vgpr_count covers them: a wave that was given fewer would have its loads land in another wave's registers) and
 # (b) nothing the compiler generates touches them.  Round 2 found a silent-corruption bug of exactly this kind on the GPU;
 # build() refuses to produce a library that has the next one (tests/test_build_guards.py runs the same check).
-GUARD_SRC = "dfx_k_partition.hip"
+GUARD_SRC = "dfx_k_pass2.hip"
 RESERVED_VGPRS = range(88, 120)
 
 
@@ -179,7 +179,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         (os.path.exists(guard_obj) and os.path.getmtime(guard_stamp) < os.path.getmtime(guard_obj))
 
     def guard(_unused=None):
-        n = check_pass2_reserved_registers(pass2_guard_asm(hipcc, os.path.join(OBJDIR, "dfx_k_partition.guard.s")))
+        n = check_pass2_reserved_registers(pass2_guard_asm(hipcc, os.path.join(OBJDIR, os.path.splitext(GUARD_SRC)[0] + ".guard.s")))
         if verbose:
             print(f"build guard: {n} instantiations of k_partition_agg_lean keep v88..v119 to the hand-written loads", flush=True)
 

@@ -128,7 +128,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b, int64_
   const bool may_spill = dec.use_partition || dec.occupied_known + ctl.unconfirmed_rows + (uint64_t)n > T.load_limit;
   // two batches can be in flight unchecked; with a deferred pass 2 every row of the window may still be spilled (by pass 2
   // itself, when its block is full)
-  // (pair scan: a row whose key finds no slot in its block is spilled once per OPERAND -- by the last plane of each, dfx_k_partition.hip --;
+  // (pair scan: a row whose key finds no slot in its block is spilled once per OPERAND -- by the last plane of each, dfx_k_pass2.hip --;
   // planes of a shared operand: once.  Their windows hold at most two batches, launch_rows)
   const int64_t window_rows = dec.use_partition ? (pair_scan() ? (int64_t)std::min(2, std::max(1, opt().partition_defer_batches)) * (split_is_shared ? 1 : 2)
                                                          : (int64_t)std::max(1, opt().partition_defer_batches)) * std::max(n, win.layout_rows) : 0;

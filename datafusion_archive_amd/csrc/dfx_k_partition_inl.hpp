@@ -20,7 +20,7 @@
 // Translation units: the pass-1 kernels below are templates over the row-source policy; every unit of the list in
 // dfx_pass1_units.hpp instantiates its policies in its own file (dfx_k_partition_<unit>.hip, one DFX_PASS1_UNIT line each:
 // dfx_k_partition_ws_inl.hpp) so that they compile in parallel; dfx_k_partition.hip holds the dispatcher (select_pass1,
-// launch_partition), pass 2 and the sizing helpers.
+// launch_partition) and the sizing helpers, dfx_k_pass2.hip pass 2 (its forms and their choice: dfx_pass2_forms.hpp).
 #pragma once
 #include "dfx_kernels_inl.hpp"
 #include "dfx_launch.hpp"
@@ -127,7 +127,6 @@ __global__ __launch_bounds__(kPBlock) void k_partition(const DevProgram P, const
   uint32_t* fill = (uint32_t*)lds;  // [n_parts] rows appended to each of this producer's regions
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
-  const int NW = (int)PT.n_words;
   const uint32_t producer = blockIdx.x;
   for (uint32_t p = threadIdx.x; p < PT.n_parts; p += kPBlock)
     fill[p] = (PT.flags & PTF_RESUME) ? PT.counts[(uint64_t)p * PT.n_producers + producer] : 0u;

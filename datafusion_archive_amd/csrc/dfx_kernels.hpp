@@ -173,7 +173,7 @@ hipError_t launch_utf8_pred(const int32_t* offsets, const uint8_t* data, const u
 // popcount per 4096-row tile of a finished bitmap (the compaction offsets of a filter whose mask is one term's bitmap)
 hipError_t launch_mask_tile_counts(const uint64_t* mask_words, uint32_t* tile_counts, int64_t n, hipStream_t s);
 
-// partitioned GROUP BY (dfx_k_partition.hip): pass 1 routes passing rows to per-(producer, partition)
+// partitioned GROUP BY (dfx_k_partition.hip, pass 2: dfx_k_pass2.hip): pass 1 routes passing rows to per-(producer, partition)
 // regions, pass 2 aggregates every partition in an LDS copy of its table block.  Single-word keys.
 size_t partition_stage_bytes(const DevPartition& PT);
 bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PLANES: ... the one-value kernels with the raw operand

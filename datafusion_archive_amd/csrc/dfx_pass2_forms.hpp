@@ -1,0 +1,105 @@
+// dfx_pass2_forms.hpp -- pass 2 of the partitioned GROUP BY: THE list of its forms and which one a launch takes.
+// choose_pass2 is everything launch_partition_agg (dfx_k_pass2.hip) decides before it launches: the form or a refusal, the
+// dynamic LDS bytes, the number of launches and what each is launched with.  A new form is one name here, its place in
+// choose_pass2 and its case in launch_partition_agg.
+// Host only and free of HIP: tests/native/pass2_forms_check.cpp holds choose_pass2 against a table written out by hand.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "dfx_device.hpp"
+
+namespace dfx {
+
+// flat_*: k_partition_agg, the producers' rows as one flattened index space (one 16-byte value / any row width).  The others are
+// k_partition_agg_lean, a wave per region: stream_wide 16-byte rows and keys in LDS; narrow 12-byte rows and tags; shared_operand
+// narrow rows, 2..kSharedMaxAggs accumulators of the one raw operand in ONE launch; planes the same rows, one launch per
+// accumulator plane; pair 20-byte rows of two operands, one launch per plane; pair_planes both.
+enum class Pass2Form : int { refused = -1, flat_one, flat_any, stream_wide, narrow, shared_operand, planes, pair, pair_planes };
+constexpr const char* kPass2FormName[] = {"flat_one", "flat_any", "stream_wide", "narrow", "shared_operand", "planes", "pair", "pair_planes"};
+
+// The twelve or sixteen bytes of a routed row that a lane of k_partition_agg_lean loads (the Rows* policies of dfx_k_pass2.hip):
+// wide {key, operand}, the block holds keys; narrow {image, operand}, the block holds 32-bit tags; pair0 {operand lo, operand hi,
+// image}: operand 0 of a 20-byte pair row; *_xf: the operand is raw, the launch applies its plane's transform.
+enum class Pass2Rows : int { wide, narrow, pair0, narrow_xf, pair0_xf };
+
+constexpr int kP2Waves = 16;          // waves of a pass-2 workgroup (kABlock / 64)
+constexpr int kP2RetryRows = 128;     // per-wave queue of rows that missed their home group (narrow rows: 12 bytes each)
+constexpr int kP2RetryRowsWide = 96;  // ... 16-byte rows: 128 KB of block + 16 x 96 x 16 B = 152 KB of LDS
+constexpr int kSharedMaxAggs = 3;     // PTF_SHARED: 4096 slots x (4-byte tag + 3 accumulators) = 112 KB of LDS
+constexpr size_t kP2LdsLimit = 160 * 1024 - 256;
+constexpr uint32_t kP2MaxProducers = 1024;  // (k_partition_agg scans the producer counts one per thread)
+
+struct Pass2Launch {
+  Pass2Rows rows = Pass2Rows::wide;
+  uint32_t operand = 0;       // pair forms: DevPartition::pair_operand
+  uint32_t plane_spills = 0;  // one launch per plane: DevPartition::plane_spills
+  bool keeps_snap = true;     // false: snap_host = nullptr (only a window's last launch publishes the control block)
+};
+struct Pass2Choice {
+  Pass2Form form = Pass2Form::refused;
+  size_t lds_bytes = 0;
+  int n_launches = 0;  // one, or one per accumulator plane: launch a aggregates plane a
+  Pass2Launch launch[kMaxAggs];
+};
+
+constexpr bool pass2_is_pair(Pass2Form f) { return f == Pass2Form::pair || f == Pass2Form::pair_planes; }
+constexpr bool pass2_per_plane(Pass2Form f) { return f == Pass2Form::planes || pass2_is_pair(f); }
+
+// Dynamic LDS of a launch.  flat_*: the block's key and accumulator planes, the prefix of the producer counts.  The others: the
+// block -- keys or 4-byte tags, and the accumulator planes of ONE launch -- and sixteen per-wave queues of parked rows.
+constexpr size_t pass2_lds_bytes(Pass2Form f, uint32_t slots, int na, uint32_t n_producers) {
+  if (f == Pass2Form::flat_one || f == Pass2Form::flat_any) return (size_t)slots * (size_t)(1 + na) * 8 + (size_t)(n_producers + 1) * 4 + 16;
+  if (f == Pass2Form::stream_wide) return (size_t)slots * 16 + (size_t)kP2Waves * kP2RetryRowsWide * 16;
+  return (size_t)slots * (size_t)(4 + 8 * (f == Pass2Form::shared_operand ? na : 1)) + (size_t)kP2Waves * kP2RetryRows * 12;
+}
+
+// flags: PT.flags; na, kw: T's; slots: of a table block (T.block_mask + 1); narrow_line: kNarrowLine.
+inline Pass2Choice choose_pass2(uint32_t flags, int na, int kw, uint32_t n_words, uint32_t slots, uint32_t n_producers, uint32_t pair_ops,
+                                bool narrow_line) {
+  const Pass2Choice refused;
+  Pass2Choice c;
+  const auto take = [&](Pass2Form f, int n_launches) {
+    c.form = f;
+    c.lds_bytes = pass2_lds_bytes(f, slots, na, n_producers);
+    c.n_launches = n_launches;
+  };
+  // An oddity, kept: the FLAT forms' bytes are checked whatever form follows, except under PTF_PAIR / PTF_PLANES (one-plane blocks
+  // fit where na planes would not) -- and a launch with one of those two flags then has no check of its own form's bytes at all.
+  if ((pass2_lds_bytes(Pass2Form::flat_any, slots, na, n_producers) > kP2LdsLimit && !(flags & (PTF_PAIR | PTF_PLANES))) || n_producers > kP2MaxProducers)
+    return refused;
+  if (!(flags & PTF_NARROW)) {
+    take(na != 1 ? Pass2Form::flat_any : ((flags & PTF_STREAM_PASS2) && n_words == 2) ? Pass2Form::stream_wide : Pass2Form::flat_one, 1);
+  } else if ((flags & PTF_SHARED) && !(flags & PTF_PLANES)) {
+    take(Pass2Form::shared_operand, 1);
+    if (na < 2 || na > kSharedMaxAggs || kw != 1 || c.lds_bytes > kP2LdsLimit) return refused;
+    c.launch[0].rows = Pass2Rows::narrow;
+  } else if (flags & PTF_SHARED) {
+    // aggregates of one operand, one launch of the one-value kernel per accumulator plane (the plane's own transform and atomic)
+    if (na < 2 || na > kMaxAggs || kw != 1) return refused;
+    take(Pass2Form::planes, na);
+    for (int a = 0; a < na; ++a) c.launch[a] = {Pass2Rows::narrow_xf, 0u, a + 1 == na ? 1u : 0u, a + 1 == na};
+  } else if (flags & PTF_PAIR) {
+    // launches of the one-value kernel over the same regions, one per accumulator plane, each on its operand; the first claims
+    // the window's new keys, the others find them, the last resets CTRL_MAX_FILL and publishes the control block
+    if (na < 2 || na > kMaxAggs || kw != 1 || !narrow_line) return refused;
+    const bool raw_ops = (flags & PTF_PLANES) != 0;  // (three and more aggregates: the launch applies the accumulator's transform)
+    take(raw_ops ? Pass2Form::pair_planes : Pass2Form::pair, na);
+    for (int a = 0; a < na; ++a) {
+      Pass2Launch& l = c.launch[a];
+      l.operand = (pair_ops >> a) & 1u;
+      l.rows = l.operand == 0u ? (raw_ops ? Pass2Rows::pair0_xf : Pass2Rows::pair0) : (raw_ops ? Pass2Rows::narrow_xf : Pass2Rows::narrow);
+      l.plane_spills = 1u;  // the last accumulator of this operand?
+      for (int b = a + 1; b < na; ++b)
+        if (((pair_ops >> b) & 1u) == l.operand) l.plane_spills = 0u;
+      l.keeps_snap = a + 1 == na;
+    }
+  } else {
+    if (na != 1 || kw != 1) return refused;
+    take(Pass2Form::narrow, 1);
+    c.launch[0].rows = Pass2Rows::narrow;
+  }
+  return c;
+}
+
+}  // namespace dfx

@@ -1,6 +1,6 @@
 """Guards for hand-scheduled device code (CPU test: hipcc cross-compiles without a GPU).
 
-k_partition_agg_lean (pass 2 of the partitioned GROUP BY, csrc/dfx_k_partition.hip) issues its row loads by inline
+k_partition_agg_lean (pass 2 of the partitioned GROUP BY, csrc/dfx_k_pass2.hip) issues its row loads by inline
 assembly into VGPRs v88..v119, which the kernel withholds from the register allocator (amdgpu_num_vgpr(88)).  That is
 only sound while (a) the code object ALLOCATES those registers (its .vgpr_count covers v119: a wave that was given fewer
 registers would have its loads land in another wave's registers) and (b) nothing the compiler generates touches them.
@@ -26,7 +26,7 @@ def pass2_asm(tmp_path_factory):
 
 
 def test_pass2_reserved_registers_are_allocated_and_untouched(pass2_asm):
-    """the check build() itself runs whenever dfx_k_partition.o is rebuilt (datafusion_archive_amd/build.py)"""
+    """the check build() itself runs whenever dfx_k_pass2.o is rebuilt (datafusion_archive_amd/build.py)"""
     from datafusion_archive_amd import build as b
     assert b.check_pass2_reserved_registers(pass2_asm) >= 8
 
