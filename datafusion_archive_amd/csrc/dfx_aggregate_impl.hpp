@@ -315,6 +315,12 @@ struct AggregateRelation::Impl {
   const uint32_t* key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt);
   bool key_shadow_asked = false;
   int64_t key_shadow_launches = 0;  // (explain)
+  // ... and the operand column's Float32 shadow (agg.value_shadow; dfx_value_shadow.hpp), only beside a bound key shadow: prog, pt are
+  // the launch's with the key already bound.  *operand_col: the slot it belongs in
+  const uint32_t* value_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt, int* operand_col);
+  size_t shadow_query_bytes() const;  // the memory rule's "what this query holds"
+  bool value_shadow_asked = false;
+  int64_t value_shadow_launches = 0;  // (explain)
   Status drain();
   Status emit_grouped(DeviceBatch* out, int64_t expected);
   std::shared_ptr<void> emit_total;  // pinned: the scan's group count

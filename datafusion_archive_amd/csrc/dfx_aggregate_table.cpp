@@ -485,15 +485,10 @@ Status AggregateRelation::Impl::finish_launched(int64_t rows, bool read_back) {
   return handle_ctrl(hc, rows);
 }
 
-const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) {
-  const AggOptions& o = opt();
-  if (o.key_shadow == 0 || calibrating || !dec.narrow || kw != 1 || !fp.valid || prog.has_nulls || !input) return nullptr;
-  const int ks = fp.keycol[0];
-  if (ks >= prog.n_cols || prog.col_dtype[ks] != T_I64 || cols.c[ks].validity) return nullptr;
-  if (!partition_key_shadow_supported(prog, fp, cols, T, pt)) return nullptr;  // (no pass-1 kernel reads this shape's key from 4-byte words)
-  ScanMemo* memo = input->scan_memo();
-  if (!memo) return nullptr;
-  hipStream_t s = ctx().stream;
+// The device side of a column shadow's build (dfx_key_shadow.hpp, dfx_value_shadow.hpp) on stream s: `launch` is the streaming
+// kernel that writes the 4-byte copy and ORs its verdict into one device word; build_us: the counter the attempt's wall time goes to.
+typedef hipError_t (*ShadowLaunch)(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* verdict, hipStream_t s);
+static KeyShadowDevice shadow_device(hipStream_t s, ShadowLaunch launch, long long* build_us) {
   KeyShadowDevice dev;
   dev.free_bytes = []() -> size_t {
     size_t free_b = 0, total_b = 0;
@@ -504,26 +499,62 @@ const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog
     return free_b;
   };
   dev.alloc = [](size_t bytes) { return device_alloc_optional(bytes); };
-  dev.narrow = [s](const void* src, int64_t rows, void* dst, uint32_t* dropped) -> bool {
-    ScopedUs t_build(&counters().agg_key_shadow_build_us);
+  dev.narrow = [s, launch, build_us](const void* src, int64_t rows, void* dst, uint32_t* dropped) -> bool {
+    ScopedUs t_build(build_us);
     std::shared_ptr<void> word = device_alloc_optional(sizeof(uint32_t));
     if (!word) return false;
     bool ok = hipMemsetAsync(word.get(), 0, sizeof(uint32_t), s) == hipSuccess;
-    ok = ok && launch_narrow_keys((const uint64_t*)src, rows, (uint32_t*)dst, (uint32_t*)word.get(), s) == hipSuccess;
+    ok = ok && launch((const uint64_t*)src, rows, (uint32_t*)dst, (uint32_t*)word.get(), s) == hipSuccess;
     ok = ok && hipMemcpyAsync(dropped, word.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     return ok;
   };
-  // what this query holds: routing regions and counts, the spill list, the table's key and accumulator planes
+  return dev;
+}
+
+// what this query holds -- routing regions and counts, the spill list, the table's key and accumulator planes --: a shadow is built
+// only if as much stays free after it
+size_t AggregateRelation::Impl::shadow_query_bytes() const {
   int widest = na();
   for (const Chunk& ch : chunks) widest = std::max(widest, ch.n);
-  const size_t query_bytes = win.rows_bytes + win.cnt_bytes + (size_t)spill.capacity * 8 * (size_t)(kw + widest) + ((size_t)T.mask + 2) * 8 * (size_t)(kw + widest);
+  return win.rows_bytes + win.cnt_bytes + (size_t)spill.capacity * 8 * (size_t)(kw + widest) + ((size_t)T.mask + 2) * 8 * (size_t)(kw + widest);
+}
+
+const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) {
+  const AggOptions& o = opt();
+  if (o.key_shadow == 0 || calibrating || !dec.narrow || kw != 1 || !fp.valid || prog.has_nulls || !input) return nullptr;
+  const int ks = fp.keycol[0];
+  if (ks >= prog.n_cols || prog.col_dtype[ks] != T_I64 || cols.c[ks].validity) return nullptr;
+  if (!partition_key_shadow_supported(prog, fp, cols, T, pt)) return nullptr;  // (no pass-1 kernel reads this shape's key from 4-byte words)
+  ScanMemo* memo = input->column_memo();
+  if (!memo) return nullptr;
+  const KeyShadowDevice dev = shadow_device(ctx().stream, launch_narrow_keys, &counters().agg_key_shadow_build_us);
   const bool first = !key_shadow_asked;
   key_shadow_asked = true;
   bool built = false;
-  const uint32_t* words = memo->key_shadows.acquire(cols.c[ks].values, o.key_shadow, first, query_bytes, dev, &built);
+  const uint32_t* words = memo->key_shadows.acquire(cols.c[ks].values, o.key_shadow, first, shadow_query_bytes(), dev, &built);
   if (built) ++counters().agg_key_shadow_builds;
+  return words;
+}
+
+// prog, pt: the launch with the key shadow bound; cols: the batch as the operator bound it (before row0).  The kernels' own
+// condition (partition_value_shadow_supported: one of the two signatures -- the operand a plain Float64 column, every predicate
+// term on it, SUM or the shared raw operand) and the operator's: no nulls, no calibration slice, a resident table below.
+const uint32_t* AggregateRelation::Impl::value_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt, int* operand_col) {
+  const AggOptions& o = opt();
+  if (o.value_shadow == 0 || calibrating || !(pt.flags & PTF_KEY4) || prog.has_nulls || !input) return nullptr;
+  int vc = 0;
+  if (!partition_value_shadow_supported(prog, fp, cols, T, pt, &vc) || cols.c[vc].validity) return nullptr;
+  ScanMemo* memo = input->column_memo();
+  if (!memo) return nullptr;
+  const ValueShadowDevice dev = shadow_device(ctx().stream, launch_narrow_values, &counters().agg_value_shadow_build_us);
+  const bool first = !value_shadow_asked;
+  value_shadow_asked = true;
+  bool built = false;
+  const uint32_t* words = memo->value_shadows.acquire(cols.c[vc].values, o.value_shadow, first, shadow_query_bytes(), dev, &built);
+  if (built) ++counters().agg_value_shadow_builds;
+  *operand_col = vc;
   return words;
 }
 
@@ -562,6 +593,17 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
       bytes -= 4.0 * (double)n;
       ++counters().agg_key_shadow_launches;
       ++key_shadow_launches;
+      // ... and the operand's Float32 shadow beside it, where every value of the column is exactly its float: 8 bytes per row.
+      // The scanners widen it back to the column's own bits; predicate, routed rows and everything behind them are what they were
+      int vc = 0;
+      if (const uint32_t* value_words = value_shadow_words(prog, fpp, cols_in, pt, &vc)) {
+        cols.c[vc].values = value_words + row0;
+        prog.col_dtype[vc] = T_F32;
+        pt.flags |= PTF_VAL4;
+        bytes -= 4.0 * (double)n;
+        ++counters().agg_value_shadow_launches;
+        ++value_shadow_launches;
+      }
     }
     // close the window when one more batch could overflow a region (or the batch budget is used up; the calibration
     // slice is aggregated at once: the strategy decision reads the group count)

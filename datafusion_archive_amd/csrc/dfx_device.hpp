@@ -318,6 +318,9 @@ enum : uint32_t {
                           // column was checked when the shadow was built).  The scanners of the two compile-time signatures load two keys per
                           // lane (StaticKey4Policy); the scan plan's kernels (PTF_PAIR included) load one 4-byte key per lane.
                           // Set per launch (launch_rows), never part of the layout
+  PTF_VAL4 = 1024u,       // with PTF_KEY4, the two compile-time signatures only: the operand column is bound to its Float32 shadow as
+                          // well (every value of the column is exactly that float: checked when the shadow was built).  Key and operand
+                          // are loaded as pair words and the operand is widened back (StaticKey4Val4Policy): 8 bytes per row.  Per launch
   PTF_NARROW = 8u         // keys below 2^32 (seen by the calibration slice): 12-byte routed rows {hash image, operand}, pass 2
                           // works on 32-bit images; needs ring flavour, one key word, one aggregate
 };

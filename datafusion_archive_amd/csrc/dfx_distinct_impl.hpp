@@ -72,6 +72,7 @@ class DistinctTap : public Relation {
   void require_columns(const std::vector<char>& needed) override;
   void explain(std::string* out, int depth) const override { input_->explain(out, depth); }  // (no line of its own)
   ScanMemo* scan_memo() override { return input_->scan_memo(); }
+  ScanMemo* column_memo() override { return input_->column_memo(); }
   void prefer_batch_rows(int64_t rows) override { input_->prefer_batch_rows(rows); }
   void host_stream_options(const HostStreamOptions& o) override { input_->host_stream_options(o); }
   Relation* input() const { return input_.get(); }

@@ -18,6 +18,7 @@
 #include "../../include/dfx.h"
 #include "dfx_device.hpp"
 #include "dfx_key_shadow.hpp"
+#include "dfx_value_shadow.hpp"
 #include "dfx_utf8_match.hpp"
 
 namespace dfx {
@@ -163,6 +164,9 @@ struct Counters {
   long long agg_key_shadow_builds = 0;    // Int32 shadows of resident Int64 key columns built (once per table and column)
   long long agg_key_shadow_launches = 0;  // pass-1 launches that read the key from its shadow (PTF_KEY4)
   long long agg_key_shadow_build_us = 0;  // ... wall time of the builds (kernel + the read-back of the dropped-halves word)
+  long long agg_value_shadow_builds = 0;    // Float32 shadows of resident Float64 operand columns built (once per table and column)
+  long long agg_value_shadow_launches = 0;  // pass-1 launches that read the operand from its shadow (PTF_VAL4: 8 bytes per row)
+  long long agg_value_shadow_build_us = 0;  // ... wall time of the build attempts (kernel + the read-back of the not-exact word)
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
   // COUNT(DISTINCT) (dfx_distinct.cpp)
   long long distinct_set_growths = 0;  // distinct sets rehashed into larger ones
@@ -251,6 +255,9 @@ struct Relation {
   // the number of groups an aggregate's calibration slice produced, keyed by a fingerprint of the fused program, so that
   // the second query of the same shape does not pay for the slice and its synchronous read-back again.
   virtual struct ScanMemo* scan_memo() { return nullptr; }
+  // ... and what holds for the table's columns as a WHOLE -- the key and value shadows, found by the address of a batch's slice --,
+  // which a scan that starts anywhere in the table may read (scan_memo() speaks of the table's first rows)
+  virtual struct ScanMemo* column_memo() { return scan_memo(); }
   // A consumer whose result does not depend on the batch width (an aggregate) may ask a source that slices RESIDENT data
   // for batches of at least `rows` rows: a scan of an HBM table then hands out one slice per routing window instead of
   // many small ones (each costs a launch).  Sources that produce batches (host streams, CSV) ignore it.
@@ -261,6 +268,7 @@ struct Relation {
 };
 struct ScanMemo {  // shared by every scan of a resident table (a `mutable` member of a const TableData): guarded
   mutable std::mutex mu;
+  ValueShadows value_shadows;  // the Float32 copies of its null-free Float64 columns that are Float32-exact (dfx_value_shadow.hpp; its own lock)
   KeyShadows key_shadows;  // the Int32 copies of the table's null-free Int64 columns (dfx_key_shadow.hpp; its own lock)
   std::vector<std::pair<uint64_t, uint64_t>> calibrated_groups;  // (program fingerprint, groups in the first 2^18 rows)
   bool lookup(uint64_t fp, uint64_t* groups) const {

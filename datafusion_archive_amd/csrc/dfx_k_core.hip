@@ -805,6 +805,29 @@ __global__ __launch_bounds__(kBlock) void k_narrow_keys(const uint64_t* __restri
   }
   if (hi != 0) atomicOr(dropped, hi);
 }
+// The Float32 shadow of a Float64 operand column (dfx_value_shadow.hpp), the same stream: two values per lane, the float of each
+// stored, "some value is not exactly its float" (shadow_narrow: THE rule, next to the scanners' shadow_widen) ORed into one word.
+__global__ __launch_bounds__(kBlock) void k_narrow_values(const uint64_t* __restrict__ in, int64_t n, uint32_t* __restrict__ out, uint32_t* __restrict__ inexact) {
+  typedef uint64_t u64x2v __attribute__((ext_vector_type(2)));
+  typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+  bool bad = false;
+  const int64_t n2 = n >> 1;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kBlock) {
+    const u64x2v v = __builtin_nontemporal_load((const u64x2v*)in + i);
+    bool r0, r1;
+    u32x2v w;
+    w.x = shadow_narrow(v.x, &r0);
+    w.y = shadow_narrow(v.y, &r1);
+    bad = bad || r0 || r1;
+    ((u32x2v*)out)[i] = w;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    bool r;
+    out[n - 1] = shadow_narrow(in[n - 1], &r);
+    bad = bad || r;
+  }
+  if (bad) atomicOr(inexact, 1u);
+}
 __global__ __launch_bounds__(kBlock) void k_fill_u32(uint32_t* __restrict__ p, uint32_t v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) p[i] = v;
 }
@@ -1358,6 +1381,12 @@ hipError_t launch_narrow_keys(const uint64_t* in, int64_t n, uint32_t* out, uint
   if (n <= 0) return hipSuccess;
   Scope sc(KID_FILL, s, 12.0 * (double)n);
   hipLaunchKernelGGL(k_narrow_keys, dim3(stream_grid((n / 2 + kBlock) / kBlock, 8)), dim3(kBlock), 0, s, in, n, out, dropped);
+  return hipGetLastError();
+}
+hipError_t launch_narrow_values(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* inexact, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  Scope sc(KID_FILL, s, 12.0 * (double)n);
+  hipLaunchKernelGGL(k_narrow_values, dim3(stream_grid((n / 2 + kBlock) / kBlock, 8)), dim3(kBlock), 0, s, in, n, out, inexact);
   return hipGetLastError();
 }
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, int64_t n, hipStream_t s) {

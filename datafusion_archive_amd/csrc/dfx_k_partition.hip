@@ -124,11 +124,16 @@ static Pass1Choice select_pass1(const DevProgram& P, const DevFastPlan& fast, co
     if ((PT.flags & PTF_WS) && !(PT.flags & PTF_PAIR) && (PT.flags & PTF_NARROW) && !plan_first && T.kw == 1) {
       DevProgram P8 = P;
       if (fast.valid && fast.keycol[0] < kMaxCols) P8.col_dtype[fast.keycol[0]] = T_I64;
+      // PTF_VAL4: ... and the operand -- the other of the two columns -- its Float32 shadow (T_F32), which the same two units
+      // widen back to the column's own values (StaticKey4Val4Policy)
+      if ((PT.flags & PTF_VAL4) && fast.valid && P.n_cols == 2 && fast.keycol[0] < 2 && P.col_dtype[1 - fast.keycol[0]] == T_F32)
+        P8.col_dtype[1 - fast.keycol[0]] = T_F64;
       const Pass1Unit sig = signature_unit(P8, fast, T, shared);
       if (sig == Pass1Unit::static_key_sum_pred2) c.unit = Pass1Unit::key4_static_key_sum_pred2;
       if (sig == Pass1Unit::static_key_sum) c.unit = Pass1Unit::key4_static_key_sum;
       if (c.unit != Pass1Unit::none) return c;
     }
+    if (PT.flags & PTF_VAL4) return c;  // (no other kernel reads an operand's shadow: partition_value_shadow_supported said so)
     select_plan_unit(P, fast, C, T, PT, &c);
     return c;
   }
@@ -179,6 +184,23 @@ bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast
   DevPartition PT4 = PT;
   PT4.flags |= PTF_KEY4;
   return select_pass1(P4, fast, C, T, PT4).unit != Pass1Unit::none;
+}
+
+// PTF_VAL4: does a pass-1 kernel read this launch's operand from 4-byte floats as well?  P, PT: the launch with the key shadow bound
+// (the key T_U32, PTF_KEY4).  Only the two signatures' kernels do: two columns, the operand a plain Float64 column that every
+// predicate term is on (sig_matches), SUM of it -- or, under PTF_SHARED, the raw operand of two or three aggregates of it.
+// *operand_col: its slot.
+bool partition_value_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT, int* operand_col) {
+  if (!(PT.flags & PTF_KEY4) || !fast.valid || P.n_cols != 2 || fast.keycol[0] >= 2) return false;
+  const int vc = 1 - fast.keycol[0];
+  if (P.col_dtype[vc] != T_F64) return false;
+  DevProgram P4 = P;
+  P4.col_dtype[vc] = T_F32;
+  DevPartition PT4 = PT;
+  PT4.flags |= PTF_VAL4;
+  const Pass1Unit unit = select_pass1(P4, fast, C, T, PT4).unit;
+  *operand_col = vc;
+  return unit == Pass1Unit::key4_static_key_sum_pred2 || unit == Pass1Unit::key4_static_key_sum;
 }
 
 // PTF_PLANES: does THIS bound batch take the wave-specialised one-value pass 1 with the aggregates' common raw operand?

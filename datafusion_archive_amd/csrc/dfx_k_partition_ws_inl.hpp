@@ -150,10 +150,15 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
         auto trip_body = [&](auto full_tag) {
           constexpr bool FULL = decltype(full_tag)::value;
           FOR_U {  // (unrolled, like the ring kernel's scan: a run-time loop over the U banks costs a scalar branch chain per group)
-            const COLV cur = col[u];
+            COLV cur = col[u];
             const uint32_t curv = cv[u];
             bool inb = true;
-            if constexpr (!FULL) inb = (w0 + u) * 64 + lane < n;
+            if constexpr (RowPairsOf<POL>::value) {  // (key and operand pair words: StaticKey4Val4Policy -- the lane's own two rows of the pair)
+              cur = POL::pair_row(col[u & ~1], u & 1);
+              if constexpr (!FULL) inb = w0 * 64 + POL::trip_row(u, lane) < n;
+            } else {
+              if constexpr (!FULL) inb = (w0 + u) * 64 + lane < n;
+            }
             u64x16 reg;
             uint32_t rv = 0;
             POL::eval(P, F, cur, curv, reg, rv, inb, err, prep);
@@ -363,7 +368,8 @@ void launch_partition_ws(const DevProgram& P, const DevFastPlan& fast, const Dev
 //   PAIR    the PAIR flavour (PTF_PAIR), for the policies that can evaluate two arguments (slot look-ups, PlanPolicyN): always
 //           eight scanners + eight routers (twelve routers' queues with two operand planes do not fit the LDS), the run-time
 //           comparison form
-template <typename RING, typename WC, typename NARROW, typename WS = void, typename DENSE = void, typename PAIR = void>
+//   VAL4    the wave-specialised policy over key AND operand shadows (PTF_VAL4);  VAL4D: of its dense split
+template <typename RING, typename WC, typename NARROW, typename WS = void, typename DENSE = void, typename PAIR = void, typename VAL4 = void, typename VAL4D = void>
 struct Pass1Policies {
   typedef RING ring;
   typedef WC wc;
@@ -371,6 +377,8 @@ struct Pass1Policies {
   typedef WS ws;
   typedef DENSE dense;
   typedef PAIR pair;
+  typedef VAL4 val4;
+  typedef VAL4D val4_dense;
 };
 
 // A unit with no other kernels launches its wave-specialised (or pair) kernel whatever the flags say: the host asks for
@@ -381,6 +389,12 @@ void launch_pass1(DFX_PASS1_ARGS) {
   if constexpr (!std::is_void<typename U::pair>::value) {
     if (!has_ws || ((PT.flags & PTF_WS) && (PT.flags & PTF_PAIR))) {
       hipLaunchKernelGGL((k_partition_ws<typename U::pair, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n);
+      return;
+    }
+  }
+  if constexpr (!std::is_void<typename U::val4>::value) {  // (select_pass1 sets PTF_VAL4 for the key4_* units only)
+    if (PT.flags & PTF_VAL4) {
+      launch_partition_ws<typename U::val4, typename U::val4_dense>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
       return;
     }
   }
@@ -396,11 +410,12 @@ void launch_pass1(DFX_PASS1_ARGS) {
   namespace dfx { void launch_pass1_##NAME(DFX_PASS1_ARGS) { launch_pass1<__VA_ARGS__>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s); } }
 
 // a compile-time signature: four row groups per trip, eight in the dense split;  ... over the key's Int32 shadow (StaticKey4Policy:
-// only the wave-specialised kernel knows it)
+// only the wave-specialised kernel knows it), and over the operand's Float32 shadow as well (StaticKey4Val4Policy, PTF_VAL4: the same
+// two units, the same trips)
 template <typename SIG>
 using StaticUnit = Pass1Policies<StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 8, SIG>>;
 template <typename SIG>
-using StaticKey4Unit = Pass1Policies<void, void, void, StaticKey4Policy<4, SIG>, StaticKey4Policy<8, SIG>>;
+using StaticKey4Unit = Pass1Policies<void, void, void, StaticKey4Policy<4, SIG>, StaticKey4Policy<8, SIG>, void, StaticKey4Val4Policy<4, SIG>, StaticKey4Val4Policy<8, SIG>>;
 
 // The scan plan's units (PlanPolicy: range tests on value images, plan words in vector registers): row groups per trip by column
 // class (NC = 2: <= 2 columns; 3: exactly 3 -- key, routed value, one more predicate column, e.g. SUM(w) WHERE v ... GROUP BY k, or
@@ -424,6 +439,8 @@ struct PlanUnit {
   typedef PlanPolicy1<NC, t.ring, GENK> narrow;
   typedef PlanPolicy1<NC, t.ws, GENK> ws;
   typedef PlanPolicy1<NC, t.dense, GENK> dense;
+  typedef void val4;
+  typedef void val4_dense;
   typedef typename std::conditional<NC >= 3 && !key4, PlanPolicyN<NC, t.ws, GENK>, void>::type pair;  // (+ the PAIR flavour: two aggregates of different operands routed by ONE scan -- PTF_PAIR, dfx_device.hpp)
 };
 // the pair scan over a 4-byte key (GENK = 4: the key in slot 0 is the only 4-byte column -- the Int32 shadow of a resident Int64 key

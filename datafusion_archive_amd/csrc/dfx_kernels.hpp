@@ -126,6 +126,9 @@ hipError_t launch_rehash(const DevTable& from, const DevTable& to, const DevRows
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, int64_t n, hipStream_t s);
 // the low halves of n 8-byte keys (in: 16-byte aligned) as 4-byte words (out: 8-byte aligned); the OR of the dropped halves is ORed into *dropped
 hipError_t launch_narrow_keys(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* dropped, hipStream_t s);
+// n Float64 values (in: 16-byte aligned) as Float32 (out: 8-byte aligned); *inexact is ORed with 1 when some value is not exactly
+// its float (dfx_value_shadow.hpp: other bits after widening back, a NaN, a Float32 denormal)
+hipError_t launch_narrow_values(const uint64_t* in, int64_t n, uint32_t* out, uint32_t* inexact, hipStream_t s);
 // device -> host-mapped pinned memory by a kernel on `s` (falls back to hipMemcpyAsync for unaligned pointers)
 hipError_t launch_copy_to_host(const void* src_device, void* dst_pinned, size_t bytes, hipStream_t s);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, int64_t n, hipStream_t s);
@@ -179,6 +182,8 @@ size_t partition_stage_bytes(const DevPartition& PT);
 bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PLANES: ... the one-value kernels with the raw operand
 bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PAIR: this bound batch fits the pair kernels
 bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT);  // PTF_KEY4: a pass-1 kernel reads this batch's key from its Int32 shadow
+// PTF_VAL4: ... and the operand from its Float32 shadow.  P, PT: the launch with the key shadow already bound (key T_U32, PTF_KEY4)
+bool partition_value_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT, int* operand_col);
 hipError_t launch_probe_wide_keys(const DevTable& T, hipStream_t s);
 size_t partition_ring_bytes(uint32_t n_words, uint32_t n_parts, int ring_rows, bool hot = false, bool narrow = false, int queue_rows = 0);
 size_t partition_ws_bytes(uint32_t n_parts, int scanner_waves, int operands = 1);  // LDS of the wave-specialised pass-1 kernel (PTF_WS)

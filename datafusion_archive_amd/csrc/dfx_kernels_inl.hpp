@@ -24,6 +24,19 @@ DEV double as_f64(uint64_t x) { return __longlong_as_double((long long)x); }
 DEV uint64_t f64_bits(double x) { return (uint64_t)__double_as_longlong(x); }
 DEV float as_f32(uint64_t x) { return __uint_as_float((uint32_t)x); }
 DEV uint64_t f32_bits(float x) { return (uint64_t)__float_as_uint(x); }
+// The Float32 shadow of a Float64 column (dfx_value_shadow.hpp).  shadow_widen is THE conversion from a shadow word back to the
+// column's value: the build kernel accepts an element only if this very function returns its bits, and the scanners call nothing
+// else.  shadow_narrow: the word stored for v, and whether v is refused -- other bits after widening, any NaN (a NaN's payload can
+// survive the round trip; none is accepted), or a Float32 denormal (zero exponent field, non-zero mantissa: whether v_cvt_f64_f32
+// flushes it is a mode of the wave, so no accepted value ever asks).  +-0, +-infinity and normal floats widen exactly in every mode.
+DEV uint64_t shadow_widen(uint32_t w) { return f64_bits((double)__uint_as_float(w)); }
+DEV uint32_t shadow_narrow(uint64_t v, bool* refused) {
+  const uint32_t w = __float_as_uint((float)as_f64(v));
+  const bool nan = (v & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
+  const bool denormal = (w & 0x7F800000u) == 0u && (w & 0x007FFFFFu) != 0u;
+  *refused = shadow_widen(w) != v || nan || denormal;
+  return w;
+}
 DEV bool get_bit(const uint8_t* bm, int64_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
 DEV int lane_id() { return (int)(threadIdx.x & 63); }
 
@@ -804,6 +817,65 @@ struct StaticKey4Policy : StaticPolicy<2, U_, SIG> {
     return (uint64_t)((lane & 1) ? hi : lo);
   }
 };
+// ... and whose OPERAND column is bound as 4-byte words too: the Float32 shadow of a resident Float64 column whose every value is
+// exactly its float (dfx_value_shadow.hpp).  Both columns then have the same layout, and both are loaded as pair words: one
+// 8-byte load per lane and column covers two row groups -- 512-byte wave instructions, 8 bytes per row.  Lane L owns rows 2 L and
+// 2 L + 1 of the pair, so a row's key and operand sit in the same lane: "group" 2j of the trip is the pair's even rows, 2j + 1 its
+// odd rows, no ds_bpermute and no select.  (Row order inside a trip does not matter to what is routed; the bounds test of the
+// ragged last trip does, and uses trip_row.)  pair_row rebuilds the row as the 8-byte binding has it -- the key zero-extended,
+// the operand widened by shadow_widen, the conversion the build checked --, and everything after it (predicate terms, FORM
+// specialisations, the routed value) is StaticPolicy's own code over those 8-byte values.
+template <int U_, typename SIG>
+struct StaticKey4Val4Policy : StaticPolicy<2, U_, SIG> {
+  typedef StaticPolicy<2, U_, SIG> Base;
+  typedef typename Base::COLV COLV;
+  static constexpr int U = U_;
+  static constexpr bool kRowPairs = true;
+  static constexpr int KC = SIG::key_col(0);
+  static_assert(SIG::NCOL == 2 && SIG::KW == 1 && U_ % 2 == 0, "one operand column beside the key; whole pairs of row groups per trip");
+  static DEV void load(const DevProgram&, const DevColumns& C, int64_t row, bool inb, COLV& col, uint32_t& cv) {  // (one row, as the 8-byte binding has it)
+    cv = 0xFFFFFFFFu;
+    col[1 - KC] = shadow_widen(__builtin_nontemporal_load((const uint32_t*)C.c[1 - KC].values + (inb ? row : 0)));
+    col[KC] = (uint64_t)__builtin_nontemporal_load((const uint32_t*)C.c[KC].values + (inb ? row : 0));
+  }
+  // U / 2 pair words per column: col[2j][c] = the elements of rows 128 j + 2 lane and + 1 of the trip (col[2j + 1] is not used).
+  // The pair index is clamped to the pair that holds the batch's last row: an odd batch reads four bytes past its last element
+  // (the next batch's first, or the padding the shadows are allocated with).
+  static DEV void load_trip(const DevColumns& C, int64_t w0, bool active, int64_t n, int lane, COLV (&col)[U], uint32_t (&cv)[U]) {
+    const int64_t r0 = active ? w0 * 64 : 0;
+    const int64_t left = n - r0;
+    const bool none = !active || left <= 0;
+    const uint32_t last = none ? 0u : (uint32_t)((left < (int64_t)U * 64 ? left : (int64_t)U * 64) - 1);
+    const uint32_t lastp = last >> 1;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      cv[u] = 0xFFFFFFFFu;
+      col[u][0] = 0;
+      col[u][1] = 0;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const uint64_t* p = (const uint64_t*)((const uint32_t*)C.c[c].values + (none ? 0 : r0));
+#pragma unroll
+      for (int j = 0; j < U / 2; ++j) {
+        const uint32_t i = (uint32_t)(j * 64 + lane);
+        col[2 * j][c] = __builtin_nontemporal_load(p + (i < lastp ? i : lastp));
+      }
+    }
+  }
+  // the row of the trip that this lane holds in "group" u (group 2j + b: row b of the lane's pair in pair word j)
+  static DEV int64_t trip_row(int u, int lane) { return (int64_t)(u >> 1) * 128 + 2 * lane + (u & 1); }
+  static DEV COLV pair_row(const COLV& pairs, int b) {
+    COLV row;
+    const uint32_t k = b ? (uint32_t)(pairs[KC] >> 32) : (uint32_t)pairs[KC];
+    const uint32_t w = b ? (uint32_t)(pairs[1 - KC] >> 32) : (uint32_t)pairs[1 - KC];
+    row[KC] = (uint64_t)k;
+    row[1 - KC] = shadow_widen(w);
+    return row;
+  }
+};
+template <typename POL, typename = void> struct RowPairsOf { static constexpr bool value = false; };
+template <typename POL> struct RowPairsOf<POL, std::enable_if_t<POL::kRowPairs>> { static constexpr bool value = true; };
 template <typename POL, typename = void> struct KeyPairsOf { static constexpr bool value = false; };
 template <typename POL> struct KeyPairsOf<POL, std::enable_if_t<POL::kKeyPairs>> { static constexpr bool value = true; };
 

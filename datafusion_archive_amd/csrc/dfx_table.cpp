@@ -58,6 +58,9 @@ Status TableScanRelation::next(DeviceBatch* out, bool* has) {
 static void register_key_shadows(TableData* t) {
   for (const DeviceColumn& c : t->columns)
     if (c.dtype == DFX_INT64 && !c.absent && c.null_count == 0 && c.length == t->num_rows) t->memo.key_shadows.add_column(c.values, c.length);
+  // ... and an operand's Float32 shadow (dfx_value_shadow.hpp): plain Float64, no nulls
+  for (const DeviceColumn& c : t->columns)
+    if (c.dtype == DFX_FLOAT64 && !c.absent && c.null_count == 0 && c.length == t->num_rows) t->memo.value_shadows.add_column(c.values, c.length);
 }
 
 namespace {
@@ -263,6 +266,7 @@ bool set_option_in(AggOptions& o, const char* key, int64_t value) {
   else if (!strcmp(key, "agg.partition_layout")) o.partition_layout = (int)value;
   else if (!strcmp(key, "agg.narrow_keys")) o.narrow_keys = (int)value;
   else if (!strcmp(key, "agg.key_shadow")) o.key_shadow = (int)value;
+  else if (!strcmp(key, "agg.value_shadow")) o.value_shadow = (int)value;
   else if (!strcmp(key, "agg.narrow_chunk16")) o.narrow_chunk16 = (int)value;
   else if (!strcmp(key, "agg.shared_operand")) o.shared_operand = (int)value;
   else if (!strcmp(key, "agg.ctrl_snapshot")) o.ctrl_snapshot = (int)value;
@@ -481,6 +485,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_key_shadow_builds")) return counters().agg_key_shadow_builds;
   if (!strcmp(name, "agg_key_shadow_launches")) return counters().agg_key_shadow_launches;
   if (!strcmp(name, "agg_key_shadow_build_us")) return counters().agg_key_shadow_build_us;
+  if (!strcmp(name, "agg_value_shadow_builds")) return counters().agg_value_shadow_builds;
+  if (!strcmp(name, "agg_value_shadow_launches")) return counters().agg_value_shadow_launches;
+  if (!strcmp(name, "agg_value_shadow_build_us")) return counters().agg_value_shadow_build_us;
   if (!strcmp(name, "agg_pair_fallbacks")) return counters().agg_pair_fallbacks;
   if (!strcmp(name, "agg_growths")) return counters().agg_growths;
   if (!strcmp(name, "agg_shared_operand_launches")) return counters().agg_shared_operand_launches;
