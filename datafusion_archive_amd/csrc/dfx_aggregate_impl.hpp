@@ -14,6 +14,7 @@
 
 #include <algorithm>
 
+#include "dfx_pass1_layout.hpp"
 #include "dfx_relation.hpp"
 #include "dfx_sigs.hpp"
 #include "dfx_utf8_dict.hpp"
@@ -237,6 +238,11 @@ struct AggregateRelation::Impl {
     for (int a = 1; a < na(); ++a)
       if (active().plan.arg[a] != active().plan.arg[0]) return false;
     return true;
+  }
+  Pass1LayoutOptions layout_options() const {  // what choose_routed_layout (dfx_pass1_layout.hpp) reads of the options
+    const AggOptions& o = opt();
+    return {o.narrow_keys, o.narrow_chunk16, o.hot_keys, o.pass2_stream, o.pass1_ws, o.pass1_ws_dense, o.pass1_ws_dense_scanners,
+            o.partition_mode, o.partition_layout, o.partition_block, o.partition_producers, o.partition_defer, o.partition_cap_rows, o.partition_pad};
   }
   bool pair_batch_ok(const DeviceBatch& b);
   Status pair_fall_back();

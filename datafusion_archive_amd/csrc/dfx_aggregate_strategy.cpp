@@ -326,10 +326,11 @@ bool AggregateRelation::Impl::pair_batch_ok(const DeviceBatch& b) {
   // the replay queues on a few addresses (Zipf(1.0), 10^9 rows: SUM(v), MIN(w) 51 ms against 12.2 for a scan per aggregate;
   // SUM(v), MIN(v) 43 ms, 96 with the all-planes blocks).  One scan per aggregate then.
   if (o.hot_keys > 0 || (o.hot_keys < 0 && dec.skew_seen)) return no("skewed keys: the one-value scans have the hot-key pairs");
-  if ((!split_is_shared && (!o.plan || !o.fast)) || o.narrow_keys == 0 || !o.narrow_chunk16 || o.pass1_ws <= 0 || o.partition_layout == 2 || ((uint32_t)o.partition_mode & 0x8Fu) != 2u) return no("options");
+  if (!split_is_shared && (!o.plan || !o.fast)) return no("options");
   if (!split_is_shared && !scan_plan_shape_ok(active().builder->program(), active().fast, kw, na(), val_xform())) return no("scan plan shape");  // (also: a predicate over nulls stays fused, consume_batch_chunk)
   const uint64_t S = (uint64_t)T.block_mask + 1;
-  if (S != 8192 || partition_ws_bytes((uint32_t)((T.mask + 1) / S), split_is_shared ? 4 : 8, split_is_shared ? 1 : 2) > (size_t)158 * 1024) return no("table blocks");
+  // (the layout's own conditions, as ensure_partition will ask them: dfx_pass1_layout.hpp)
+  if (S != 8192 || !pair_layout_fits(layout_options(), (uint32_t)((T.mask + 1) / S), split_is_shared)) return no("layout options or table blocks");
   if (b.num_rows <= 0) return true;
   DevProgram prog;
   DevColumns cols;

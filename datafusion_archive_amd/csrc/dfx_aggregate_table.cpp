@@ -79,7 +79,6 @@ Status AggregateRelation::Impl::ensure_spill(int64_t rows) {
   return Status::OK();
 }
 
-// scratch for the partitioned strategy, sized for a batch of `rows` rows (worst case: all pass)
 // the active chunk's 2..3 aggregates all take the same operand (AVG's SUM and COUNT, SUM + MIN + MAX of one column ...):
 // with narrow keys and no nulls in this batch, routed rows carry that one operand (PTF_SHARED)
 bool AggregateRelation::Impl::shared_operand() const {
@@ -89,170 +88,41 @@ bool AggregateRelation::Impl::shared_operand() const {
   return true;
 }
 
+// scratch for the partitioned strategy, sized for a batch of `rows` rows (worst case: all pass).  The policy -- which pass-1 flavour
+// routes the rows, the row form, the regions' geometry -- is choose_routed_layout (dfx_pass1_layout.hpp)
 Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now) {
-  const uint64_t S = (uint64_t)T.block_mask + 1;
-  const bool raw_ok = !nulls_now || (has_pred && !unfused_now);  // (a raw operand has no validity: fine under an absorbed predicate -- every surviving slot is valid)
-  const bool want_planes = pair_planes() && dec.narrow && opt().narrow_keys != 0 && raw_ok && same_operand_all() && kNarrowLine && opt().narrow_chunk16 &&
-                           opt().pass1_ws > 0 && opt().partition_layout != 2 && ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
-                           partition_ws_bytes((uint32_t)((T.mask + 1) / S), 4, 1) <= (size_t)158 * 1024;
-  const bool want_shared = !pair_scan() && dec.narrow && opt().narrow_keys != 0 && !nulls_now && shared_operand() &&
-                           ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
-                           partition_ring_bytes(2, (uint32_t)((T.mask + 1) / S), 16, false, true, 128) <= (size_t)158 * 1024;
-  const bool want_pair = pair_scan() && !split_is_shared && !want_shared && dec.narrow && kw == 1 && na() >= 2 && split_distinct == 2 && (na() == 2 || raw_ok) && kNarrowLine && opt().narrow_keys != 0 && opt().narrow_chunk16 &&
-                         opt().pass1_ws > 0 && opt().partition_layout != 2 && ((uint32_t)opt().partition_mode & 0x8Fu) == 2u &&
-                         partition_ws_bytes((uint32_t)((T.mask + 1) / S), 8, 2) <= (size_t)158 * 1024;
-  if (pair_scan() && !want_pair && !want_planes)  // (a table block holds ONE accumulator plane in this mode: no other routed form fits; until the
-    return Status::Err(DFX_NOT_IMPLEMENTED, "pair scan: not for this table");  // next batch boundary the rows go through the global table)
-  const bool want_narrow = dec.narrow && kw == 1 && (na() == 1 || want_shared || want_pair || want_planes) && opt().narrow_keys != 0;
-  const uint32_t n_words = (want_shared || want_planes) ? 2u : (uint32_t)(kw + na());
-  if (win.layout_valid && rows <= win.layout_rows && PT.n_parts == (uint32_t)((T.mask + 1) / S) && PT.n_words == n_words &&
-      ((PT.flags & PTF_NARROW) != 0) == want_narrow && ((PT.flags & PTF_SHARED) != 0) == (want_shared || want_planes) && ((PT.flags & PTF_PAIR) != 0) == want_pair &&
-      ((PT.flags & PTF_PLANES) != 0) == (want_planes || (want_pair && na() > 2)))
+  RoutedLayoutQuery q = {};
+  q.rows = rows, q.nulls_now = nulls_now, q.kw = kw, q.na = na();
+  q.table_slots = T.mask + 1, q.block_slots = (uint64_t)T.block_mask + 1, q.cu_count = device_cu_count();
+  q.phase = !pair_scan() ? PairPhase::none : split_is_shared ? PairPhase::planes : PairPhase::pair;
+  q.split_distinct = split_distinct, q.split_ops = split_ops, q.split_arg1 = split_arg1;
+  q.shared_operand = shared_operand(), q.same_operand_all = same_operand_all();
+  q.has_pred = has_pred, q.unfused_now = unfused_now;
+  q.narrow = dec.narrow, q.dense_seen = dec.dense_seen, q.mostly_seen = dec.mostly_seen, q.skew_seen = dec.skew_seen;
+  q.opt = layout_options();
+  const RoutedLayout L = choose_routed_layout(q);
+  if (L.kind == RoutedLayoutKind::refused_pair_scan) return Status::Err(DFX_NOT_IMPLEMENTED, "pair scan: not for this table");
+  const uint32_t form = PTF_NARROW | PTF_SHARED | PTF_PAIR | PTF_PLANES;
+  if (win.layout_valid && rows <= win.layout_rows && PT.n_parts == L.PT.n_parts && PT.n_words == L.PT.n_words && (PT.flags & form) == L.want_flags)
     return Status::OK();  // same table, a batch the regions were sized for: keep appending
   DFX_RETURN_IF_ERROR(flush_pass2());  // rows routed under the old layout
   win.layout_valid = false;
-  memset(&PT, 0, sizeof(PT));
-  PT.n_parts = (uint32_t)((T.mask + 1) / S);
-  PT.n_words = n_words;
-  int ps = 0;
-  while ((1ull << ps) < S) ++ps;
-  PT.part_shift = (uint32_t)ps;
-  if (PT.n_parts > 4096) return Status::Err(DFX_NOT_IMPLEMENTED, "partitioned strategy: too many table blocks");
-  // pass-1 flavour (agg.partition_mode).  Scattered 16-byte stores are transaction-bound at ~87 G rows/s on
-  // MI355X while runs of >= 64 bytes reach > 400 G rows/s (tools/ubench2.hip), so routed rows are write-combined
-  // in LDS whenever the partition count allows it:
-  //   2 (default)  lock-free per-partition LDS rings, 128-byte chunks, no barrier in the scan loop
-  //   1            workgroup-wide LDS counting sort (also for partition counts whose rings do not fit LDS)
-  //   0            one 16-byte store per row straight from registers (very many partitions)
-  const AggOptions& o = opt();
-  const uint32_t block = o.partition_block == 512 ? 512u : 1024u;
-  const size_t budget = block == 512 ? (size_t)79 * 1024 : (size_t)156 * 1024;
-  const uint32_t sort_cap = partition_sort_capacity(PT.n_words, PT.n_parts, block, budget);
-  const int want = o.partition_mode & 15;
-  if (want_shared) {
-    PT.flags |= PTF_NARROW | PTF_SHARED;
-    PT.mode = 2u;
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
-  } else if (want_planes) {
-    PT.flags |= PTF_NARROW | PTF_CHUNK16 | PTF_WS | PTF_SHARED | PTF_PLANES;
-    PT.ws_scanners = (o.pass1_ws == 4 || (dec.mostly_seen && o.pass1_ws_dense_scanners == 4)) ? 4u : 8u;  // (as for one aggregate)
-    PT.mode = 2u;
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
-  } else if (want_pair) {
-    PT.flags |= PTF_NARROW | PTF_CHUNK16 | PTF_WS | PTF_PAIR;
-    if (na() > 2) PT.flags |= PTF_PLANES;  // raw operands, a transform per accumulator in pass 2
-    PT.pair_ops = split_ops;
-    PT.pair_arg1 = split_arg1;
-    PT.ws_scanners = 8u;
-    PT.mode = 2u;
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
-  } else if (want == 2 && partition_ring_bytes(PT.n_words, PT.n_parts, 16) <= (size_t)158 * 1024) {
-    const bool hot = o.hot_keys > 0 || (o.hot_keys < 0 && dec.skew_seen);
-    const bool chunks8 = !((uint32_t)o.partition_mode & 0x80u);
-    if (want_narrow && chunks8) PT.flags |= PTF_NARROW;
-    if (hot && na() == 1 && chunks8 && partition_ring_bytes(PT.n_words, PT.n_parts, 16, true, (PT.flags & PTF_NARROW) != 0) <= (size_t)158 * 1024)
-      PT.flags |= PTF_HOT;
-    if ((PT.flags & PTF_NARROW) && !(PT.flags & PTF_HOT) && o.narrow_chunk16 && !(kNarrowLine && o.partition_layout == 2) /* LINE chunks: contiguous regions */ &&
-        partition_ring_bytes(PT.n_words, PT.n_parts, kNarrowRingRows, false, true) <= (size_t)158 * 1024)
-      PT.flags |= PTF_CHUNK16;
-    // selective scans: the scanning and the routing belong to different waves (dfx_k_partition_ws_inl.hpp).  When most rows
-    // pass, every wave has rows to route all the time and the ring kernel's symmetric waves are the better fit
-    // (round 5, 2^26-row launches, us per launch: ring kernel / 8 + 8 waves / 4 + 12 waves -- selectivity 0.2: - / 415 / 535; 0.5: 326 /
-    // 261 / 292; 0.8: 403 / 371 / 353; every row routed: 434 / 438 / 417-424 -- profiles/r05_pass1_ws_by_selectivity.txt.  So: always
-    // the wave-specialised kernel, four scanners once more than two thirds of the rows are routed.  agg.pass1_ws_dense = -1: never
-    // above one half, round 4's rule)
-    const bool ws_fits = o.pass1_ws_dense >= 0 || !dec.dense_seen;
-    if ((PT.flags & PTF_CHUNK16) && o.pass1_ws > 0 && ws_fits && !(((uint32_t)o.partition_mode) & ~15u)) {
-      // the split: 8 scanners + 8 routers; dense scans (more than half of the rows routed): 4 + 12 (agg.pass1_ws_dense_scanners)
-      PT.ws_scanners = (o.pass1_ws == 4 || (dec.mostly_seen && o.pass1_ws_dense_scanners == 4)) ? 4u : 8u;  // (agg.pass1_ws = 4: that split whatever the selectivity -- tests)
-      if (partition_ws_bytes(PT.n_parts, (int)PT.ws_scanners) <= (size_t)158 * 1024) PT.flags |= PTF_WS;
-    }
-    PT.mode = 2u | ((uint32_t)o.partition_mode & ~15u);
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
-  } else if (want == 2 && partition_ring_bytes(PT.n_words, PT.n_parts, 8) <= (size_t)158 * 1024) {
-    // several aggregates: rows of 3+ words.  8-row rings (two 4-row chunks) still fit where 16-row ones do not
-    PT.mode = 2u | 0x100u;
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-    if (o.partition_producers > 0) PT.n_producers = (uint32_t)std::min(1024, o.partition_producers);
-  } else if (want != 0 && PT.n_parts <= 1024 && sort_cap >= 4 * PT.n_parts) {
-    PT.mode = 1u | ((uint32_t)o.partition_mode & ~15u);
-    PT.block = block;
-    PT.stage_rows = sort_cap;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count() * (int)(1024 / block));
-  } else {
-    // one producer workgroup (1024 lanes) per CU: producers x partitions x 128 B of open region lines
-    PT.mode = 0;
-    PT.block = 1024;
-    PT.stage_rows = 0;
-    PT.n_producers = (uint32_t)std::min(1024, device_cu_count());
-  }
-  const uint64_t avg = (uint64_t)rows / ((uint64_t)PT.n_producers * PT.n_parts) + 1;
-  // capacities are whole 64-row trips; LINE chunks (ten rows per 128-byte line, PTF_CHUNK16): whole lines as well
-  const uint64_t capq = (PT.flags & PTF_PAIR) ? (uint64_t)kPairCapQuantum : ((PT.flags & PTF_CHUNK16) && kNarrowLine) ? (uint64_t)kNarrowCapQuantum : 64ull;
-  win.worst = (uint32_t)((2 * avg + 64 + capq - 1) / capq * capq);
-  // regions hold `window` worst-case batches.  Deferral pays when few rows are routed (headline, 20 %: 2 batches per
-  // pass 2 = -3 % per query); when most rows are, the twice-as-long regions cost pass 1 more than the saved launches
-  // give back (config 3, 1e9 rows: 11.05 ms at 2, 10.08 ms at 1)
-  int window = o.partition_defer > 0 ? std::min(o.partition_defer, 16) : (int)std::max<int64_t>(1, std::min<int64_t>(8, ((int64_t)1 << 27) / std::max<int64_t>(rows, 1)));
-  if (dec.dense_seen) window = 1;
-  PT.cap_rows = win.worst * (uint32_t)window;
-  if (o.partition_cap_rows > 0) {  // tests: tiny regions (overflow -> spill list); no deferral
-    PT.cap_rows = (uint32_t)(((uint64_t)o.partition_cap_rows + capq - 1) / capq * capq);
-    win.worst = PT.cap_rows;
-  }
-  if (o.pass2_stream && na() == 1 && kw == 1) PT.flags |= PTF_STREAM_PASS2;
-  uint64_t pad_words = (uint64_t)(o.partition_pad >= 0 ? o.partition_pad : 0) / 8;
-  if ((PT.flags & PTF_CHUNK16) && kNarrowLine) pad_words = (pad_words + 15) / 16 * 16;  // (every region starts on a 128-byte line)
-  size_t row_bytes;
-  const bool line_chunks = (PT.flags & PTF_CHUNK16) && kNarrowLine;  // a region is cap_rows / 10 lines of 128 bytes
-  const bool pair_rows = (PT.flags & PTF_PAIR) != 0;  // ... cap_rows / 6 lines
-  const uint64_t region_words = pair_rows ? (uint64_t)(PT.cap_rows / (uint32_t)kPairChunkRows) * 16u
-                                : line_chunks ? (uint64_t)(PT.cap_rows / (uint32_t)kNarrowChunkRows) * (kNarrowSlotBytes / 8)
-                                : (PT.flags & PTF_NARROW) ? (uint64_t)PT.cap_rows * 12 / 8 : (uint64_t)PT.cap_rows * PT.n_words;
-  // one pass-2 trip's worth (64 contiguous rows, or six LINE chunks = 60 rows: 768 bytes either way): regions are contiguous (layouts 0 and 1)
-  PT.win_stride = pair_rows ? (uint64_t)(kPairTripBytes / 8u) : line_chunks ? 96u : region_words / (PT.cap_rows / 64);
-  if (o.partition_layout == 2) {  // windowed: window w of every partition of a producer side by side
-    PT.part_stride = PT.win_stride;
-    PT.win_stride = (uint64_t)PT.n_parts * PT.part_stride;
-    PT.prod_stride = (uint64_t)(PT.cap_rows / 64) * PT.win_stride + pad_words;
-    row_bytes = sizeof(uint64_t) * (size_t)PT.n_producers * PT.prod_stride;
-  } else if (o.partition_layout == 0) {  // partition-major (round 1)
-    PT.prod_stride = region_words;
-    PT.part_stride = (uint64_t)PT.n_producers * PT.prod_stride + pad_words;
-    row_bytes = sizeof(uint64_t) * (size_t)PT.n_parts * PT.part_stride;
-  } else {  // producer-major
-    PT.part_stride = region_words;
-    PT.prod_stride = (uint64_t)PT.n_parts * PT.part_stride + pad_words;
-    row_bytes = sizeof(uint64_t) * (size_t)PT.n_producers * PT.prod_stride;
-  }
-  const size_t cnt_bytes = sizeof(uint32_t) * (size_t)PT.n_parts * PT.n_producers;
+  PT = L.PT;
+  if (L.kind == RoutedLayoutKind::refused_table_blocks) return Status::Err(DFX_NOT_IMPLEMENTED, "partitioned strategy: too many table blocks");
+  win.worst = L.worst;
   Status st;
   ScopedUs t_alloc(&counters().agg_alloc_us);
-  if (!win.rows || win.rows_bytes < row_bytes) {
+  if (!win.rows || win.rows_bytes < L.row_bytes) {
     win.rows.reset();
-    win.rows = device_alloc(row_bytes, &st);
+    win.rows = device_alloc(L.row_bytes, &st);
     if (!win.rows) return st;
-    win.rows_bytes = row_bytes;
+    win.rows_bytes = L.row_bytes;
   }
-  if (!win.counts || win.cnt_bytes < cnt_bytes) {
+  if (!win.counts || win.cnt_bytes < L.cnt_bytes) {
     win.counts.reset();
-    win.counts = device_alloc(cnt_bytes, &st);
+    win.counts = device_alloc(L.cnt_bytes, &st);
     if (!win.counts) return st;
-    win.cnt_bytes = cnt_bytes;
+    win.cnt_bytes = L.cnt_bytes;
   }
   PT.rows = (uint64_t*)win.rows.get();
   PT.counts = (uint32_t*)win.counts.get();

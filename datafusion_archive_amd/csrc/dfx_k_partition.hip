@@ -1,8 +1,7 @@
 // dfx_k_partition.hip -- partitioned GROUP BY: the pass-1 dispatcher (select_pass1, launch_partition), the probe for wide keys
-// (k_probe_wide_keys) and the sizing helpers.  The pass-1 kernels and the description of the strategy are in
-// dfx_k_partition_inl.hpp; their instantiations are in dfx_k_partition_<unit>.hip, one file per unit of dfx_pass1_units.hpp;
-// pass 2 is dfx_k_pass2.hip.
-#define DFX_PARTITION_MAIN_TU
+// (k_probe_wide_keys).  The pass-1 kernels and the description of the strategy are in dfx_k_partition_inl.hpp; their
+// instantiations are in dfx_k_partition_<unit>.hip, one file per unit of dfx_pass1_units.hpp; the kernels' LDS bytes and what
+// launch_partition accepts (partition_launchable) are in dfx_pass1_layout.hpp; pass 2 is dfx_k_pass2.hip.
 #include "dfx_k_partition_ws_inl.hpp"
 
 namespace dfx {
@@ -26,25 +25,6 @@ hipError_t launch_probe_wide_keys(const DevTable& T, hipStream_t s) {
   if (T.kw != 1) return hipSuccess;
   hipLaunchKernelGGL(k_probe_wide_keys, dim3(1024), dim3(256), 0, s, T);
   return hipGetLastError();
-}
-
-size_t partition_stage_bytes(const DevPartition& PT) {
-  if ((PT.mode & 15u) == 0) return (size_t)PT.n_parts * 4 + 16;
-  if ((PT.mode & 15u) == 2 && (PT.flags & PTF_WS)) return partition_ws_bytes(PT.n_parts, PT.ws_scanners == 4 ? 4 : 8, (PT.flags & PTF_PAIR) ? 2 : 1);
-  if ((PT.mode & 15u) == 2)
-    return partition_ring_bytes(PT.n_words, PT.n_parts, (PT.flags & PTF_CHUNK16) ? kNarrowRingRows : (PT.mode & 0x100u) ? 8 : 16, (PT.flags & PTF_HOT) != 0,
-                                (PT.flags & PTF_NARROW) != 0, (PT.flags & PTF_SHARED) ? 128 : 0);
-  return (size_t)PT.stage_rows * ((size_t)PT.n_words * 8 + 4) + (size_t)PT.n_parts * 12 + (2 + 16) * 4 + 16;
-}
-
-// LDS rows of the write-combining buffer for a workgroup of `block` lanes and an LDS budget
-uint32_t partition_sort_capacity(uint32_t n_words, uint32_t n_parts, uint32_t block, size_t lds_budget) {
-  const size_t fixed = (size_t)n_parts * 12 + (2 + 16) * 4 + 16;
-  if (lds_budget <= fixed) return 0;
-  size_t cap = (lds_budget - fixed) / ((size_t)n_words * 8 + 4);
-  cap = cap / block * block;
-  if (cap > (size_t)kSortMaxCap) cap = kSortMaxCap;
-  return (uint32_t)cap;
 }
 
 // the pass-1 units (dfx_pass1_units.hpp; dfx_k_partition_<unit>.hip defines launch_pass1_<unit>)
@@ -221,12 +201,7 @@ hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const 
                             double algo_bytes, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   Scope sc(KID_PARTITION, s, algo_bytes);
-  const size_t lds_bytes = partition_stage_bytes(PT);
-  if ((PT.mode & 15u) == 0 && lds_bytes > 65536) return hipErrorInvalidValue;
-  if ((PT.mode & 15u) == 2 && lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  if ((PT.mode & 15u) == 1 && (lds_bytes > 160 * 1024 || PT.stage_rows == 0 || PT.stage_rows > (uint32_t)kSortMaxCap ||
-                       PT.n_parts > 4096 || (PT.block != 512 && PT.block != 1024)))
-    return hipErrorInvalidValue;
+  if (!partition_launchable(PT)) return hipErrorInvalidValue;
   const Pass1Choice c = select_pass1(P, fast, C, T, PT);
   if (c.unit == Pass1Unit::none) return hipErrorNotSupported;
   kPass1Launch[(int)c.unit](P, c.bound ? c.fp : fast, c.bound ? c.cp : C, plan, T, c.PT, spill, n, c.lds_bytes, s);

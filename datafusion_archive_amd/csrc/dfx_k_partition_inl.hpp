@@ -20,10 +20,12 @@
 // Translation units: the pass-1 kernels below are templates over the row-source policy; every unit of the list in
 // dfx_pass1_units.hpp instantiates its policies in its own file (dfx_k_partition_<unit>.hip, one DFX_PASS1_UNIT line each:
 // dfx_k_partition_ws_inl.hpp) so that they compile in parallel; dfx_k_partition.hip holds the dispatcher (select_pass1,
-// launch_partition) and the sizing helpers, dfx_k_pass2.hip pass 2 (its forms and their choice: dfx_pass2_forms.hpp).
+// launch_partition), dfx_pass1_layout.hpp the kernels' LDS bytes and the choice of the routed layout, dfx_k_pass2.hip pass 2 (its
+// forms and their choice: dfx_pass2_forms.hpp).
 #pragma once
 #include "dfx_kernels_inl.hpp"
 #include "dfx_launch.hpp"
+#include "dfx_pass1_layout.hpp"
 #include "dfx_pass1_units.hpp"
 
 namespace dfx {
@@ -220,8 +222,7 @@ __global__ __launch_bounds__(kPBlock) void k_partition(const DevProgram P, const
 // permutation) and copies it out in sorted order: adjacent lanes then write adjacent rows of the
 // same region.  The hash is computed once per PASSING row at full lane utilisation, not once per
 // scanned row.  A flush round is six barriers; all waves take part in every round (a wave that has
-// finished its input keeps joining rounds until every wave has finished).
-constexpr int kSortMaxCap = 8192;  // LDS buffer rows (upper bound: 13-bit row index in the permutation word)
+// finished its input keeps joining rounds until every wave has finished).  (kSortMaxCap: dfx_pass1_layout.hpp)
 
 DEV uint32_t mbcnt64(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -477,10 +478,7 @@ __global__ __launch_bounds__(BLOCK) void k_partition_sorted(const DevProgram P, 
 // Leftover partial chunks are written row by row at the end.
 // ring rows per partition kRingRP = rows per chunk (CH: 4 or 8) x chunks (NCH).  (An 8-row ring with two
 // workgroups per CU -- 32 waves -- was measured ~20 % slower than 16 rows and one workgroup.)
-constexpr int ring_queue_rows(int rp) { return rp == 16 ? 192 : 128; }  // (32- and 30-row rings: 96 KB of ring, 128-row queues)  // (32-row rings: 16-row chunks of 12-byte rows need the LDS)
-constexpr int kRingBlock = 1024;
-constexpr int kHotSlots = 1024;        // hot-key pairs per pass-1 workgroup, 16-byte rows
-constexpr int kHotSlotsNarrow = 2048;  // ... with 12-byte rows (the ring is 16 KB smaller)
+// (kRingBlock, ring_queue_rows, kHotSlots and the kernel's LDS bytes, partition_ring_bytes: dfx_pass1_layout.hpp)
 #ifndef DFX_RING_DEPTH
 #define DFX_RING_DEPTH 1
 #endif
@@ -493,17 +491,6 @@ struct RingLds {
   uint32_t* commit;  // [n_parts][kRingNCH]
   uint32_t* gen;     // [n_parts][kRingNCH]
 };
-
-#ifdef DFX_PARTITION_MAIN_TU  // a plain function: defined once, in dfx_k_partition.hip
-size_t partition_ring_bytes(uint32_t n_words, uint32_t n_parts, int kRingRP, bool hot, bool narrow, int queue_rows) {
-  const int kRingQ = queue_rows > 0 ? queue_rows : ring_queue_rows(kRingRP);
-  const size_t ring = (narrow && kNarrowLine && kRingRP == kNarrowRingRows) ? (size_t)n_parts * kNarrowRingSlots * kNarrowSlotBytes
-                                                                            : (size_t)n_parts * kRingRP * (narrow ? 12 : n_words * 8);
-  return ring + (size_t)(kRingBlock / 64) * kRingQ * n_words * 8 +
-         (size_t)(kRingBlock / 64) * 64 * (kRingRP >= 16 ? 8 : 4) + (size_t)n_parts * 4 * (1 + 2 * 4) + 64 +
-         (hot ? (size_t)(narrow ? kHotSlotsNarrow : kHotSlots) * 16 : 0);
-}
-#endif
 
 #define WG_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
 

@@ -24,25 +24,7 @@
 
 namespace dfx {
 
-constexpr int kWsQueueRows = 256;  // per scanner wave (power of two): 3 KB {u32 key, u64 operand}
-constexpr int kWsCH = kNarrowChunkRows, kWsRP = kNarrowRingRows, kWsNCH = kWsRP / kWsCH;  // (dfx_device.hpp: LINE chunks of ten rows, three slots)
-
-struct WsCtl {  // one per queue (= per router wave)
-  uint32_t tail;  // rows produced (written by the queue's scanner)
-  uint32_t head;  // rows consumed (written by its router)
-  uint32_t done;  // the scanner has published its last row
-  uint32_t pad;
-};
-
-#ifdef DFX_PARTITION_MAIN_TU
-size_t partition_ws_bytes(uint32_t n_parts, int ns, int nv) {  // nv: routed operands per row (2: PTF_PAIR -- a second operand plane per queue)
-  const int nq = kRingBlock / 64 - ns;  // one queue per ROUTER wave (a scanner feeds (16 - ns) / ns of them in turn)
-  return (size_t)n_parts * kNarrowRingSlots * kNarrowSlotBytes + (size_t)(kRingBlock / 64) * 64 * 8 /* jobs */ + (size_t)n_parts * 4 * (1 + 2 * kWsNCH) +
-         (size_t)nq * kWsQueueRows * (4 + 8 * (size_t)nv) + (size_t)nq * sizeof(WsCtl) + 64;
-}
-#else
-size_t partition_ws_bytes(uint32_t n_parts, int ns, int nv);
-#endif
+// (kWsQueueRows, kWsCH / kWsRP / kWsNCH, WsCtl and the kernel's LDS bytes, partition_ws_bytes: dfx_pass1_layout.hpp)
 
 // rows the narrow routed form cannot carry: a key >= 2^32 (the claim sentinel i64::MIN among them).  No row of a stream whose
 // calibration slice saw narrow keys only takes this path unless the data changes under it.  They go to the spill list and

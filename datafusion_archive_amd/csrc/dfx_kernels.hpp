@@ -177,17 +177,14 @@ hipError_t launch_utf8_pred(const int32_t* offsets, const uint8_t* data, const u
 hipError_t launch_mask_tile_counts(const uint64_t* mask_words, uint32_t* tile_counts, int64_t n, hipStream_t s);
 
 // partitioned GROUP BY (dfx_k_partition.hip, pass 2: dfx_k_pass2.hip): pass 1 routes passing rows to per-(producer, partition)
-// regions, pass 2 aggregates every partition in an LDS copy of its table block.  Single-word keys.
-size_t partition_stage_bytes(const DevPartition& PT);
+// regions, pass 2 aggregates every partition in an LDS copy of its table block.  Single-word keys.  (The LDS bytes of pass 1 and the
+// routed layout a table takes: dfx_pass1_layout.hpp.)
 bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PLANES: ... the one-value kernels with the raw operand
 bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PAIR: this bound batch fits the pair kernels
 bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT);  // PTF_KEY4: a pass-1 kernel reads this batch's key from its Int32 shadow
 // PTF_VAL4: ... and the operand from its Float32 shadow.  P, PT: the launch with the key shadow already bound (key T_U32, PTF_KEY4)
 bool partition_value_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT, int* operand_col);
 hipError_t launch_probe_wide_keys(const DevTable& T, hipStream_t s);
-size_t partition_ring_bytes(uint32_t n_words, uint32_t n_parts, int ring_rows, bool hot = false, bool narrow = false, int queue_rows = 0);
-size_t partition_ws_bytes(uint32_t n_parts, int scanner_waves, int operands = 1);  // LDS of the wave-specialised pass-1 kernel (PTF_WS)
-uint32_t partition_sort_capacity(uint32_t n_words, uint32_t n_parts, uint32_t block, size_t lds_budget);
 hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,
                             const DevTable& T, const DevPartition& PT, const DevRows& spill, int64_t n,
                             double algo_bytes, hipStream_t s);

@@ -23,4 +23,4 @@ def test_pass2_has_its_translation_unit():
     assert B.GUARD_SRC == "dfx_k_pass2.hip" and B.GUARD_SRC in B.SOURCES
     assert "dfx_pass2_forms.hpp" in B.HEADERS
     text = open(os.path.join(B.CSRC, B.GUARD_SRC)).read()
-    assert "DFX_PARTITION_MAIN_TU" not in text  # the plain functions that macro guards stay defined once, in dfx_k_partition.hip
+    assert "DFX_PARTITION_MAIN_TU" not in text  # (the macro that once kept pass 1's sizing functions in one translation unit; they are inline in dfx_pass1_layout.hpp now)
