@@ -172,6 +172,10 @@ struct Counters {
   long long distinct_set_growths = 0;  // distinct sets rehashed into larger ones
   long long distinct_spill_rows = 0;   // rows replayed from a distinct set's spill list
   long long distinct_inserted = 0;     // tuples in the distinct sets at emit
+  // ORDER BY / LIMIT (dfx_sort.cpp; tests/test_gpu_sort_cases.py): they observe, they decide nothing
+  long long sort_passes_run = 0;      // radix passes launched (count + scan + scatter of one varying digit)
+  long long sort_passes_skipped = 0;  // digits found constant over the input: no pass
+  long long sort_topk_selects = 0;    // ORDER BY ... LIMIT k queries whose candidates were radix-selected
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;

@@ -1,7 +1,8 @@
 // dfx_sort.cpp -- SortRelation and LimitRelation: LogicalPlan::Sort / LogicalPlan::Limit (logicalplan.rs:313-338), which
 // the reference's planner produces for ORDER BY / LIMIT (sqlplanner.rs:142-183) and its executor leaves at
 // `unimplemented!()` (context.rs:113,194).  SURVEY.md section 8(f) rank 4.  No reference behaviour exists, so the
-// semantics are defined here and in the oracle (tests/oracle.py sort_batches / limit_batches), PARITY UNPINNED:
+// semantics are defined here and restated twice for the tests (tests/oracle.py sort_batches / limit_batches and, by another
+// method, tests/sort_cases.py; the two are held against each other on the CPU):
 //   * ORDER BY e1 [ASC|DESC], e2 ...: stable; NULL is larger than every value (last when ascending, first when
 //     descending); NaN is larger than every number; the result is ONE batch (like the aggregate's);
 //   * sort keys: any scalar expression of a fixed-width type, or a Utf8 COLUMN (byte-wise lexicographic order, like Rust's
@@ -162,7 +163,11 @@ Status SortRelation::sort_by_key(const std::vector<DeviceBatch>& batches, int ke
       bool constant = false;
       for (int b = 0; b < 256; ++b)
         if (hh[d * 256 + b] == (uint64_t)m) constant = true;
-      if (constant) continue;  // every element has the same digit: the pass would be the identity
+      if (constant) {  // every element has the same digit: the pass would be the identity
+        ++counters().sort_passes_skipped;
+        continue;
+      }
+      ++counters().sort_passes_run;
       DFX_HIP(launch_radix_count((const uint64_t*)img_a.get(), m, 8 * d, (uint32_t*)counts.get(), s));
       DFX_HIP(launch_scan_u32((const uint32_t*)counts.get(), (uint64_t*)offsets.get(), 256 * tiles, (uint64_t*)tmp.get(), s));
       DFX_HIP(launch_radix_scatter((const uint64_t*)img_a.get(), (const uint32_t*)idx_a.get(), m, 8 * d,
@@ -253,6 +258,7 @@ Status SortRelation::select_candidates(const std::vector<DeviceBatch>& batches, 
   DFX_HIP(hipStreamSynchronize(s));
   *idx = cand;
   *m = (int64_t)kept;
+  ++counters().sort_topk_selects;
   return Status::OK();
 }
 

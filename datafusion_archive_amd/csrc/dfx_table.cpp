@@ -505,6 +505,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "distinct_set_growths")) return counters().distinct_set_growths;
   if (!strcmp(name, "distinct_spill_rows")) return counters().distinct_spill_rows;
   if (!strcmp(name, "distinct_inserted")) return counters().distinct_inserted;
+  if (!strcmp(name, "sort_passes_run")) return counters().sort_passes_run;
+  if (!strcmp(name, "sort_passes_skipped")) return counters().sort_passes_skipped;
+  if (!strcmp(name, "sort_topk_selects")) return counters().sort_topk_selects;
   if (!strcmp(name, "xchg_calls")) return counters().xchg_calls;
   if (!strcmp(name, "xchg_local_us")) return counters().xchg_local_us;
   if (!strcmp(name, "xchg_wait_peers_us")) return counters().xchg_wait_peers_us;

@@ -523,7 +523,10 @@ int32_t dfx_set_option(const char* key, int64_t value);
  *   "agg_fewgroup_launches"       launches of the register-accumulator kernel (at most 8 groups known)
  *   "agg_hot_key_launches"        pass-1 launches that kept heavy keys in LDS
  *   "agg_unfused_batches"         batches filtered for real because of nulls under the absorbed predicate
- *   "distinct_set_growths", "distinct_spill_rows"  COUNT(DISTINCT) sets rehashed into larger ones / rows replayed from their spill lists */
+ *   "distinct_set_growths", "distinct_spill_rows"  COUNT(DISTINCT) sets rehashed into larger ones / rows replayed from their spill lists
+ * ORDER BY / LIMIT (they observe only; tests/test_gpu_sort_cases.py):
+ *   "sort_passes_run", "sort_passes_skipped"   radix passes launched / digits found constant over the input and skipped
+ *   "sort_topk_selects"           ORDER BY ... LIMIT k queries whose candidates were radix-selected by the first key */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 

@@ -6,6 +6,7 @@ The product package never imports this module.  It converts pyarrow arrays to th
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import subprocess
 from typing import List, Optional, Sequence
@@ -379,29 +380,42 @@ def read_csv(filename: str, schema: pa.Schema, batch_size: int = 1024) -> List[p
 
 # ---------------------------------------------------------------------------------------------------
 # ORDER BY / LIMIT (LogicalPlan::Sort / Limit, logicalplan.rs:313-338).  The reference's executor has neither
-# (context.rs:113,194: unimplemented!()), so this restates the SEMANTICS THE LIBRARY DEFINES, independently and
-# naively (pure Python, small inputs only) -- PARITY UNPINNED: stable; NULL larger than every value; NaN larger than
-# every number; one result batch.
+# (context.rs:113,194: unimplemented!()), so this restates the SEMANTICS THE LIBRARY DEFINES,
+# independently and naively (pure Python, small inputs only): stable; NULL larger than every value; every NaN equal and
+# larger than every number; -0.0 < +0.0; one result batch.  No reference behaviour pins it; a second restatement of
+# another construction does (tests/sort_cases.py reference_sort, compared on the CPU by tests/test_sort_cases_host.py).
 # ---------------------------------------------------------------------------------------------------
-def sort_batches(batches: Sequence[pa.RecordBatch], keys: Sequence[tuple]) -> Optional[pa.RecordBatch]:
-    """keys: [(Expr, asc)] -- the inner expressions of Expr::Sort, evaluated with the oracle's own evaluator."""
+def sort_order(batches: Sequence[pa.RecordBatch], keys: Sequence[tuple]) -> List[int]:
+    """The permutation behind sort_batches: output row i is row order[i] of the concatenated non-empty batches."""
     batches = [b for b in batches if b.num_rows]
-    if not batches:
-        return None
-    table = pa.Table.from_batches(batches).combine_chunks()
     key_cols = []
     for e, _asc in keys:
         key_cols.append(pa.concat_arrays([eval_expr(e, b) for b in batches]).to_pylist())
-    order = list(range(table.num_rows))
+    order = list(range(sum(b.num_rows for b in batches)))
     for (_e, asc), col in reversed(list(zip(keys, key_cols))):  # least significant key first, stable sorts
         def rank(i, col=col):
             v = col[i]
             if v is None:
-                return (1, 0, 0)
-            if isinstance(v, float) and v != v:
-                return (0, 1, 0)
-            return (0, 0, v)
+                return (1, 0, 0, 0)
+            if isinstance(v, float):
+                if v != v:
+                    return (0, 1, 0, 0)  # every NaN, whatever its sign or payload
+                return (0, 0, v, math.copysign(1.0, v))  # Python's -0.0 == 0.0: the sign orders the two zeros, -0.0 first
+            return (0, 0, v, 0)
         order = sorted(order, key=rank, reverse=not asc)  # reverse=True keeps the input order of equal elements
+    return order
+
+
+def sort_batches(batches: Sequence[pa.RecordBatch], keys: Sequence[tuple]) -> Optional[pa.RecordBatch]:
+    """keys: [(Expr, asc)] -- the inner expressions of Expr::Sort, evaluated with the oracle's own evaluator.
+    The order is DESIGN.md section 9's, signed zeros included (-0.0 < +0.0).  tests/sort_cases.py holds a second reference
+    of another construction (numpy ranks + lexsort) and tests/test_sort_cases_host.py holds the two against each other,
+    bit for bit, on every case the device is later checked with."""
+    batches = [b for b in batches if b.num_rows]
+    if not batches:
+        return None
+    table = pa.Table.from_batches(batches).combine_chunks()
+    order = sort_order(batches, keys)
     return table.take(pa.array(order, pa.int64())).to_batches()[0] if table.num_rows else None
 
 
