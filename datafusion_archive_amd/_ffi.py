@@ -77,7 +77,7 @@ EXPORTED_SYMBOLS = [
     "dfx_profile_enable", "dfx_profile_reset", "dfx_profile_count", "dfx_profile_get", "dfx_set_option",
     "dfx_counter_get", "dfx_counter_reset", "dfx_relation_explain", "dfx_relation_drain_device", "dfx_filter_debug_mask",
     "dfx_debug_group_hash", "dfx_debug_unhash32", "dfx_debug_plan_term", "dfx_debug_utf8_term",
-    "dfx_csv_write", "dfx_debug_format_value",
+    "dfx_csv_write", "dfx_debug_format_value", "dfx_parquet_datasource_new",
 ]
 
 _lib = None
@@ -154,6 +154,8 @@ def lib() -> ctypes.CDLL:
                                         P(ArrowSchema), P(ArrowArrayStream)] + c_err
     L.dfx_limit_relation_new.argtypes = [P(ArrowArrayStream), ctypes.c_int64, P(ArrowSchema), P(ArrowArrayStream)] + c_err
     L.dfx_csv_datasource_new.argtypes = [ctypes.c_char_p, P(ArrowSchema), ctypes.c_int64, P(ArrowArrayStream)] + c_err
+    L.dfx_parquet_datasource_new.argtypes = [ctypes.c_char_p, P(ctypes.c_int32), ctypes.c_int32, ctypes.c_int64, P(ArrowArrayStream)] + c_err
+    L.dfx_parquet_datasource_new.restype = ctypes.c_int32
     L.dfx_aggregate_partial_build.argtypes = [P(ArrowArrayStream), ctypes.c_int32, P(ctypes.c_int32),
                                               P(ctypes.c_int64)] + c_err
     L.dfx_aggregate_partial_export.argtypes = [P(ArrowArrayStream), ctypes.c_void_p, ctypes.c_int64] + c_err

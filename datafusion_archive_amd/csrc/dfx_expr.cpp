@@ -30,6 +30,12 @@
 //       a null slot that passes the predicate is the value its bytes spell, the empty string for an Arrow-built null.)  Another declared return type: the InternalError of a numeric mismatch; more GROUP BY
 //       expressions than COUNT_DISTINCT takes: NotImplemented; both at creation (dfx_distinct.cpp folds the extrema from the distinct
 //       set of the argument at emit, dfx_k_utf8agg.hip).  Parity unpinned.
+//   D12 The Parquet data source (declared three times, executed nowhere: FileType::Parquet / `STORED AS PARQUET`, dfparser.rs:31-36,
+//       :177-178; DataSourceMeta::ParquetFile { filename, schema, projection }, datasource.rs:87-92; LogicalPlan::ParquetFile in the
+//       push-down rule, sqlplanner.rs:525-532): dfx_parquet_datasource_new (dfx_parquet.cpp) serves the file's own schema, flat
+//       required / optional leaves of BOOLEAN, INT32 / INT64 with their Int annotations, FLOAT, DOUBLE and String byte arrays, from
+//       UNCOMPRESSED chunks of dictionary, V1 and V2 pages in PLAIN, RLE_DICTIONARY and RLE; anything else is NotImplemented at
+//       construction.  Parity unpinned; the contract is pyarrow's reader.
 #include <charconv>
 #include <string.h>
 #include <strings.h>

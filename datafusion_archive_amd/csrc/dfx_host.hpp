@@ -176,6 +176,14 @@ struct Counters {
   long long sort_passes_run = 0;      // radix passes launched (count + scan + scatter of one varying digit)
   long long sort_passes_skipped = 0;  // digits found constant over the input: no pass
   long long sort_topk_selects = 0;    // ORDER BY ... LIMIT k queries whose candidates were radix-selected
+  // Parquet source (dfx_parquet.cpp; tests/test_gpu_parquet.py): they observe, they decide nothing
+  long long parquet_chunk_bytes = 0;     // bytes of column chunks copied to the device
+  long long parquet_pages = 0;           // pages walked (dictionary pages included)
+  long long parquet_dict_pages = 0;      // ... data pages whose values are dictionary indices
+  long long parquet_plain_pages = 0;     // ... data pages of PLAIN values
+  long long parquet_rle_runs = 0;        // RLE runs the kernels walked (levels, indices, RLE Booleans)
+  long long parquet_bitpacked_runs = 0;  // ... bit-packed runs
+  long long parquet_host_walked_strings = 0;  // length prefixes of PLAIN byte arrays the host chased (dictionary pages, PLAIN data pages)
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;
@@ -238,7 +246,7 @@ struct HostStreamOptions {
 };
 
 enum RelationKind { REL_HOST_STREAM, REL_TABLE_SCAN, REL_FILTER, REL_PROJECT, REL_AGGREGATE, REL_CSV, REL_SORT, REL_LIMIT,
-                    REL_DISTINCT_AGGREGATE, REL_DISTINCT_TAP };
+                    REL_DISTINCT_AGGREGATE, REL_DISTINCT_TAP, REL_PARQUET };
 
 // trait Relation (src/execution/relation.rs:27-32)
 struct Relation {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "dfx_device.hpp"
+#include "dfx_parquet_rle.hpp"
 #include "dfx_utf8_match.hpp"
 
 namespace dfx {
@@ -36,6 +37,7 @@ enum KernelId : int {
   KID_UTF8_PRED,
   KID_UTF8_EXTREMA,
   KID_CSV_WRITE,
+  KID_PARQUET,
   KID_COUNT_
 };
 const char* kernel_name(int kid);
@@ -206,6 +208,32 @@ hipError_t launch_csv_parse(const uint8_t* buf, const uint64_t* row_start, int64
                             const DevCsvPlan& plan, double avg_record_bytes, int wave_tiles, double algo_bytes, hipStream_t s);
 hipError_t launch_csv_utf8_gather(const uint8_t* buf, const uint64_t* row_start, int64_t r0, int64_t nb, int field,
                                   const int32_t* offsets, const uint64_t* starts, uint8_t* out, hipStream_t s);
+
+// Parquet column chunk -> Arrow column (dfx_k_parquet.hip, deviation D12).  One column chunk of one row group: `chunk` is the
+// chunk's bytes on the device, `pages` its host-validated page table (dfx_parquet_rle.hpp: every extent inside the chunk).
+struct DevPqColumn {
+  const uint8_t* chunk;
+  const PqPage* pages;
+  uint32_t n_pages;
+  uint32_t rows;      // of the row group
+  uint32_t optional;  // 1: definition levels -> validity
+  uint32_t dtype;     // the Arrow type stored (dfx_datatype)
+  uint32_t width;     // bytes of a stored PLAIN value (4 / 8; 0: Boolean, Utf8)
+  uint32_t dict_off, dict_n;  // the dictionary's PLAIN values (fixed width: dict_n * width bytes inside the chunk)
+  const uint32_t* dict_str;   // Utf8: offsets of the dictionary's length prefixes, dict_n + 1
+  const uint32_t* str_offs;   // Utf8: the same for PLAIN data pages (PqPage::str_base, PqPage::pad entries + 1 per page)
+  uint64_t* validity;      // optional: (rows + 63) / 64 + 1 words, zeroed
+  uint64_t* dense_bits;    // RLE Boolean pages: (sum of num_values + 63) / 64 + 1 words, zeroed
+  uint32_t* dense_idx;     // dictionary pages: sum of num_values entries
+  uint32_t* word_rank;     // optional: WalkedChunk::rank_total entries
+  uint32_t* page_nonnull;  // n_pages
+  uint32_t* page_decoded;  // n_pages
+  uint32_t* ctrl;          // CTRL_WORDS words: PQ_ERR_* bits are ORed into CTRL_ERROR
+  uint64_t* stats;         // zeroed: [0] RLE runs walked, [1] bit-packed runs, [2] null rows, [3] Utf8: bytes of all rows (64-bit sum)
+};
+// out: the values (fixed width, Boolean words); Utf8: out_starts / out_lens, rows entries each (source offsets into the chunk, lengths)
+hipError_t launch_pq_decode(const DevPqColumn& C, bool has_rle_bool, bool has_dict, void* out, int32_t* out_starts, int32_t* out_lens,
+                            double algo_bytes, hipStream_t s);
 
 // ORDER BY (dfx_k_sort.hip): order-preserving key images, stable LSD radix sort of (image, row) pairs, gathers
 hipError_t launch_sort_image(const void* values, const uint8_t* validity, int64_t bit_offset, uint8_t dtype, int asc, int64_t n,

@@ -508,6 +508,13 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "sort_passes_run")) return counters().sort_passes_run;
   if (!strcmp(name, "sort_passes_skipped")) return counters().sort_passes_skipped;
   if (!strcmp(name, "sort_topk_selects")) return counters().sort_topk_selects;
+  if (!strcmp(name, "parquet_chunk_bytes")) return counters().parquet_chunk_bytes;
+  if (!strcmp(name, "parquet_pages")) return counters().parquet_pages;
+  if (!strcmp(name, "parquet_dict_pages")) return counters().parquet_dict_pages;
+  if (!strcmp(name, "parquet_plain_pages")) return counters().parquet_plain_pages;
+  if (!strcmp(name, "parquet_rle_runs")) return counters().parquet_rle_runs;
+  if (!strcmp(name, "parquet_bitpacked_runs")) return counters().parquet_bitpacked_runs;
+  if (!strcmp(name, "parquet_host_walked_strings")) return counters().parquet_host_walked_strings;
   if (!strcmp(name, "xchg_calls")) return counters().xchg_calls;
   if (!strcmp(name, "xchg_local_us")) return counters().xchg_local_us;
   if (!strcmp(name, "xchg_wait_peers_us")) return counters().xchg_wait_peers_us;

@@ -211,6 +211,22 @@ class CsvDataSource(Relation):
         self._schema = schema
 
 
+class ParquetDataSource(Relation):
+    """DataSourceMeta::ParquetFile { filename, schema, projection } (datasource.rs:87-92), which the reference declares and never
+    executes (deviation D12).  The schema comes from the file; `projection` is a list of leaf-column indices (None: all, in file
+    order); `batch_size` <= 0 gives one batch per row group, otherwise slices of batch_size rows rounded up to a multiple of 64.
+    Uncompressed column chunks are decoded on the device; a consumer's projection push-down keeps the chunks of unread columns
+    on disk."""
+
+    def __init__(self, filename: str, projection: Optional[Sequence[int]] = None, batch_size: int = 0):
+        super().__init__()
+        err = _errbuf()
+        proj = None if projection is None else (ctypes.c_int32 * max(len(projection), 1))(*[int(i) for i in projection])
+        code = _ffi.lib().dfx_parquet_datasource_new(os.fsencode(filename), proj, 0 if projection is None else len(projection), batch_size,
+                                                     ctypes.byref(self._stream), err, 1024)
+        _check(code, err)
+
+
 class FilterRelation(Relation):
     """filter::FilterRelation::new(input, expr, schema) (filter.rs:36)."""
 

@@ -336,6 +336,31 @@ int32_t dfx_csv_datasource_new(const char* filename, const struct ArrowSchema* s
                                struct ArrowArrayStream* out, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
+ * Parquet data source.  The executor of DataSourceMeta::ParquetFile { filename, schema, projection } (src/execution/
+ * datasource.rs:87-92; `STORED AS PARQUET`, dfparser.rs:177-178), which the reference declares and never runs.  Deviation D12,
+ * parity unpinned; the contract is pyarrow's reader: the concatenated batches equal pyarrow.parquet.read_table bit for bit.
+ *   schema      from the file ("a Parquet file that contains schema information"): names, Arrow types, nullable = the field is
+ *               `optional`.  projection == NULL: every leaf column in file order; otherwise the named columns in the given order
+ *               (an index out of range is DFX_INVALID_COLUMN).
+ *   batches     a row group is decoded as a whole on the device, when the first get_next() needs it (so a consumer's projection
+ *               push-down has been heard: the chunks of columns nobody reads are neither read from the file nor copied).
+ *               batch_size <= 0: one batch per row group; > 0: zero-copy slices of batch_size rows rounded up to a multiple of
+ *               64, the last of a row group short.  A batch never spans row groups; a row group of 0 rows yields none.
+ *   subset      flat schemas (required / optional leaves under the root); BOOLEAN, INT32 (+ Int(8/16/32, s/u) by truncation), INT64
+ *               (+ Int(64, s/u)), FLOAT, DOUBLE, BYTE_ARRAY annotated String; codec UNCOMPRESSED only (there is no decompressor on
+ *               the device); dictionary pages, data pages V1 and V2; PLAIN, RLE_DICTIONARY / PLAIN_DICTIONARY, RLE Booleans; a chunk
+ *               that falls back from its dictionary to PLAIN pages.  Anything else is DFX_NOT_IMPLEMENTED at construction, naming
+ *               the column and the thing -- also for a column the projection leaves out: the subset is a property of the file.
+ *   errors      a missing or unreadable file is DFX_IO_ERROR; a file that is not Parquet or is damaged (magic, footer length,
+ *               thrift overrunning its buffer, extents beyond the file or chunk, value counts that do not add up, a run overrunning
+ *               its page, a dictionary index beyond the dictionary, a string length overrunning its page) is DFX_PARSER_ERROR
+ *               saying what and where; no device is DFX_EXECUTION_ERROR (there is no host decoding path).
+ * The stream is a library stream: operators stacked on it never leave the device.
+ * ---------------------------------------------------------------------------------------- */
+int32_t dfx_parquet_datasource_new(const char* filename, const int32_t* projection, int32_t n_projection, int64_t batch_size,
+                                   struct ArrowArrayStream* out, char* err, size_t errlen);
+
+/* ------------------------------------------------------------------------------------------
  * CSV writer.  The executor of PhysicalPlan::Write { plan, filename, kind } -- "execute a logical plan and write the output
  * to a file" (src/execution/physicalplan.rs:24-29) -- which the reference declares and never runs; kind = CSV.  A sink: it
  * consumes `input` to its end (a stream of this library stays on the device, a foreign stream is uploaded like any operator
@@ -526,7 +551,13 @@ int32_t dfx_set_option(const char* key, int64_t value);
  *   "distinct_set_growths", "distinct_spill_rows"  COUNT(DISTINCT) sets rehashed into larger ones / rows replayed from their spill lists
  * ORDER BY / LIMIT (they observe only; tests/test_gpu_sort_cases.py):
  *   "sort_passes_run", "sort_passes_skipped"   radix passes launched / digits found constant over the input and skipped
- *   "sort_topk_selects"           ORDER BY ... LIMIT k queries whose candidates were radix-selected by the first key */
+ *   "sort_topk_selects"           ORDER BY ... LIMIT k queries whose candidates were radix-selected by the first key
+ * Parquet source (they observe only; tests/test_gpu_parquet.py):
+ *   "parquet_chunk_bytes"         bytes of column chunks copied to the device -- what projection push-down saves
+ *   "parquet_pages"               pages walked by the host (dictionary pages included)
+ *   "parquet_dict_pages", "parquet_plain_pages"   data pages whose values are dictionary indices / PLAIN values
+ *   "parquet_rle_runs", "parquet_bitpacked_runs"  runs of the RLE / bit-packed hybrid the kernels walked (levels, indices, RLE Booleans)
+ *   "parquet_host_walked_strings" length prefixes of PLAIN byte arrays the host chased (dictionary pages always, PLAIN data pages) */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 

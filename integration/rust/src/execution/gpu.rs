@@ -122,6 +122,8 @@ extern "C" {
                                                out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_csv_datasource_new(filename: *const c_char, schema: *const ArrowSchema, batch_size: i64,
                               out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
+    fn dfx_parquet_datasource_new(filename: *const c_char, projection: *const i32, n_projection: i32, batch_size: i64,
+                                  out: *mut ArrowArrayStream, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_csv_write(input: *mut ArrowArrayStream, filename: *const c_char, options: *const DfxOption, n_options: i32,
                      rows_out: *mut i64, bytes_out: *mut i64, err: *mut c_char, errlen: usize) -> i32;
     fn dfx_sort_relation_new(input: *mut ArrowArrayStream, exprs: *const *const DfxRuntimeExpr, ascending: *const i32,
@@ -619,6 +621,18 @@ impl GpuRelation {
         let mut cs = export_schema(&schema);
         let code = unsafe { dfx_csv_datasource_new(name.as_ptr(), &cs, batch_size as i64, &mut *out, err.as_mut_ptr(), ERRLEN) };
         unsafe { release_schema(&mut cs) };
+        check(code, &err)?;
+        Self::from_stream(out, schema)
+    }
+    /// DataSourceMeta::ParquetFile { filename, schema, projection } (datasource.rs:87-92; the reference has no executor): a leaf that
+    /// decodes uncompressed column chunks on the GPU.  `schema` is the one the meta carries (the library serves the file's own: it
+    /// must describe the projected columns); batch_size 0: one batch per row group
+    pub fn parquet(filename: &str, schema: Arc<Schema>, projection: Option<Vec<usize>>, batch_size: usize) -> Result<Self> {
+        let (mut out, mut err) = (Self::new_out(), [0 as c_char; ERRLEN]);
+        let name = CString::new(filename).unwrap();
+        let proj: Option<Vec<i32>> = projection.map(|p| p.iter().map(|i| *i as i32).collect());
+        let (ptr, n) = match &proj { Some(p) => (p.as_ptr(), p.len() as i32), None => (std::ptr::null(), 0) };
+        let code = unsafe { dfx_parquet_datasource_new(name.as_ptr(), ptr, n, batch_size as i64, &mut *out, err.as_mut_ptr(), ERRLEN) };
         check(code, &err)?;
         Self::from_stream(out, schema)
     }
