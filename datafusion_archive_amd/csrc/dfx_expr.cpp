@@ -34,7 +34,7 @@
 //       :177-178; DataSourceMeta::ParquetFile { filename, schema, projection }, datasource.rs:87-92; LogicalPlan::ParquetFile in the
 //       push-down rule, sqlplanner.rs:525-532): dfx_parquet_datasource_new (dfx_parquet.cpp) serves the file's own schema, flat
 //       required / optional leaves of BOOLEAN, INT32 / INT64 with their Int annotations, FLOAT, DOUBLE and String byte arrays, from
-//       UNCOMPRESSED chunks of dictionary, V1 and V2 pages in PLAIN, RLE_DICTIONARY and RLE; anything else is NotImplemented at
+//       UNCOMPRESSED or LZ4_RAW chunks of dictionary, V1 and V2 pages in PLAIN, RLE_DICTIONARY and RLE; anything else is NotImplemented at
 //       construction.  Parity unpinned; the contract is pyarrow's reader.
 #include <charconv>
 #include <string.h>

@@ -184,6 +184,11 @@ struct Counters {
   long long parquet_rle_runs = 0;        // RLE runs the kernels walked (levels, indices, RLE Booleans)
   long long parquet_bitpacked_runs = 0;  // ... bit-packed runs
   long long parquet_host_walked_strings = 0;  // length prefixes of PLAIN byte arrays the host chased (dictionary pages, PLAIN data pages)
+  long long parquet_inflated_pages = 0;          // pages of compressed chunks whose block the device inflated (dictionary pages included)
+  long long parquet_stored_pages = 0;            // ... V2 pages the writer left uncompressed (is_compressed false): copied
+  long long parquet_inflated_bytes = 0;          // bytes of inflated image produced (the pages' uncompressed sizes less V2's level prefixes)
+  long long parquet_lz4_sequences = 0;           // LZ4 sequences the inflate kernel parsed (summed on the device)
+  long long parquet_inflated_bytes_to_host = 0;  // bytes of inflated image copied back for the host's walk of BYTE_ARRAY length chains
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;

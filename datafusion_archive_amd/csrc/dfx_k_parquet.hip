@@ -1,4 +1,4 @@
-// dfx_k_parquet.hip -- uncompressed Parquet column chunks -> Arrow columns on the device (deviation D12; the executor of
+// dfx_k_parquet.hip -- Parquet column chunks (UNCOMPRESSED, or LZ4_RAW inflated here first) -> Arrow columns on the device (deviation D12; the executor of
 // DataSourceMeta::ParquetFile, src/execution/datasource.rs:87-92, which the reference declares and never runs).  The host has
 // copied a chunk's bytes to HBM and walked its page HEADERS (dfx_parquet_meta.hpp: walk_chunk); the page table it uploads
 // (dfx_parquet_rle.hpp: PqPage) holds, per data page, the extents of the levels and of the values, all inside the chunk.
@@ -20,6 +20,10 @@
 //                  expanded Boolean bits -- in the column's Arrow width (null slots 0; Boolean rows as one ballot word per wave;
 //                  Utf8 rows as a source offset and a length, for the offset scan and the byte gather that follow).  A chunk that
 //                  starts dictionary-encoded and falls back to PLAIN pages is therefore handled page by page.
+//
+// A compressed chunk (codec 7, LZ4_RAW) takes one kernel more, in front of the four: k_pq_inflate, at the end of this file, one wave
+// per page of the chunk (dictionary page included), inflates or copies every page body into the INFLATED IMAGE, which `chunk` then
+// names; the page table's extents lie inside the image (dfx_parquet_meta.hpp: walk_headers, walk_bodies).
 //
 // Bounds.  Every offset taken from file bytes -- a run's payload, a value's position, a dictionary index, a string's extent (the
 // host walked the length chains and uploads them) -- is checked against the page's extent before it is used; a violation sets a
@@ -310,6 +314,86 @@ hipError_t launch_pq_decode(const DevPqColumn& C, bool has_rle_bool, bool has_di
   if (has_dict) hipLaunchKernelGGL(k_pq_dict, dim3(page_grid), dim3(kPqBlock), 0, s, C);
   const int row_grid = (int)(((uint64_t)C.rows + kPqBlock - 1) / kPqBlock);
   hipLaunchKernelGGL(k_pq_plain, dim3(row_grid), dim3(kPqBlock), 0, s, C, out, out_starts, out_lens);
+  return hipGetLastError();
+}
+
+// ---- the inflate stage ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Stores of earlier sequences -> loads of this match, between lanes of ONE wave.  The wave's stores are drained (vmcnt counts
+// stores on gfx9) inside a workgroup-scope release / acquire pair: the lanes of a wave share their CU's L1, which is written
+// through and holds no stale copy of a line this CU stored to once the store has completed, so no cache needs invalidating; the
+// fences keep the compiler from moving the stores below or the loads above the wait.  (The wait is spelled out in asm as well:
+// the compiler may drop a fence's own wait where it believes the counter empty.)
+DEV void pq_stores_visible_to_wave() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// One wave per page.  The sequences are parsed wave-uniformly (every lane runs lz4_next_sequence over the same bytes: the block is
+// read-only here); the copies are spread over the 64 lanes.  All extents of a sequence were checked by the parser before a byte of
+// it moves, against the page's extents the host checked against the chunk and the image: nothing is read or stored outside either.
+__global__ __launch_bounds__(kPqBlock) void k_pq_inflate(const DevPqInflate I) {
+  const uint32_t p = (uint32_t)((blockIdx.x * kPqBlock + threadIdx.x) >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (p >= I.n_pages) return;
+  const PqInflatePage pg = I.pages[p];
+  const uint8_t* body = I.chunk + pg.src_off;
+  uint8_t* page = I.image + pg.dst_off;
+  for (uint32_t i = lane; i < pg.prefix_len; i += 64) page[i] = body[i];  // V2: the levels are never compressed
+  const uint8_t* src = body + pg.prefix_len;
+  uint8_t* out = page + pg.prefix_len;
+  const uint32_t src_len = pg.src_len - pg.prefix_len, out_len = pg.dst_len - pg.prefix_len;
+  uint32_t sequences = 0;
+  if (!(pg.flags & PQ_INFLATE_COMPRESSED)) {
+    for (uint32_t i = lane; i < out_len; i += 64) out[i] = src[i];  // a stored page (out_len == src_len: the header pass)
+  } else if (src_len != 0 || out_len != 0) {
+    uint64_t pos = 0, produced = 0;
+    for (;;) {
+      Lz4Seq q;
+      if (!lz4_next_sequence(src, src_len, pos, produced, out_len, &q)) {
+        if (lane == 0) pq_raise(I.ctrl, PQ_ERR_INFLATE);  // the page's remainder stays zero
+        break;
+      }
+      ++sequences;
+      for (uint32_t i = lane; i < q.lit_len; i += 64) out[produced + i] = src[q.lit_pos + i];
+      produced += q.lit_len;
+      if (q.last) break;
+      // byte i of the match is byte (i mod offset) of the `offset` bytes before it: only bytes produced before the match began are
+      // read, so an overlapping match (offset 1 included) has no dependence between the lanes of one copy
+      pq_stores_visible_to_wave();
+      const uint8_t* from = out + (produced - q.offset);
+      for (uint32_t i = lane; i < q.match_len; i += 64) out[produced + i] = from[i % q.offset];
+      produced += q.match_len;
+      pos = q.next;
+    }
+  }
+  // the page's prologue: lanes 0-3 load the bytes of the word at body offset 0, lanes 4-7 those of the word at the probe offset
+  pq_stores_visible_to_wave();
+  uint32_t mine = (lane < 4 && lane < pg.dst_len) ? (uint32_t)page[lane] << (8 * lane) : 0u;
+  uint32_t word0 = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) word0 |= __shfl(mine, k, 64);
+  const uint64_t at = pq_probe_offset(pg, word0) + (lane & 3u);
+  mine = (lane >= 4 && lane < 8 && at < pg.dst_len) ? (uint32_t)page[at] << (8 * (lane & 3u)) : 0u;
+  uint32_t probe = 0;
+#pragma unroll
+  for (int k = 4; k < 8; ++k) probe |= __shfl(mine, k, 64);
+  if (lane == 0) {
+    I.prologues[p].word0 = word0;
+    I.prologues[p].probe = probe;
+    if (sequences) atomicAdd((unsigned long long*)I.stats, (unsigned long long)sequences);
+  }
+}
+
+}  // namespace
+
+hipError_t launch_pq_inflate(const DevPqInflate& I, double image_bytes, hipStream_t s) {
+  if (I.n_pages == 0) return hipSuccess;
+  Scope sc(KID_PARQUET_INFLATE, s, image_bytes);
+  const int page_grid = (int)(((uint64_t)I.n_pages * 64 + kPqBlock - 1) / kPqBlock);
+  hipLaunchKernelGGL(k_pq_inflate, dim3(page_grid), dim3(kPqBlock), 0, s, I);
   return hipGetLastError();
 }
 

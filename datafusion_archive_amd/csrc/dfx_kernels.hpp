@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "dfx_device.hpp"
+#include "dfx_parquet_lz4.hpp"
 #include "dfx_parquet_rle.hpp"
 #include "dfx_utf8_match.hpp"
 
@@ -38,6 +39,7 @@ enum KernelId : int {
   KID_UTF8_EXTREMA,
   KID_CSV_WRITE,
   KID_PARQUET,
+  KID_PARQUET_INFLATE,
   KID_COUNT_
 };
 const char* kernel_name(int kid);
@@ -231,6 +233,18 @@ struct DevPqColumn {
   uint32_t* ctrl;          // CTRL_WORDS words: PQ_ERR_* bits are ORed into CTRL_ERROR
   uint64_t* stats;         // zeroed: [0] RLE runs walked, [1] bit-packed runs, [2] null rows, [3] Utf8: bytes of all rows (64-bit sum)
 };
+// The inflate stage of a compressed chunk (k_pq_inflate), run before the kernels above: every page of `pages` (the host's header
+// pass checked every extent: dfx_parquet_lz4.hpp) is inflated or copied from `chunk` into `image`, which DevPqColumn::chunk then names.
+struct DevPqInflate {
+  const uint8_t* chunk;        // the chunk as the file holds it
+  uint8_t* image;              // the inflated image, zeroed: a page whose block is malformed keeps zeros from the bad sequence on
+  const PqInflatePage* pages;
+  uint32_t n_pages;
+  PqPrologue* prologues;       // n_pages: what the host's body pass reads of each inflated page
+  uint32_t* ctrl;              // CTRL_WORDS words: PQ_ERR_INFLATE is ORed into CTRL_ERROR
+  uint64_t* stats;             // zeroed: [0] sequences parsed
+};
+hipError_t launch_pq_inflate(const DevPqInflate& I, double image_bytes, hipStream_t s);
 // out: the values (fixed width, Boolean words); Utf8: out_starts / out_lens, rows entries each (source offsets into the chunk, lengths)
 hipError_t launch_pq_decode(const DevPqColumn& C, bool has_rle_bool, bool has_dict, void* out, int32_t* out_starts, int32_t* out_lens,
                             double algo_bytes, hipStream_t s);

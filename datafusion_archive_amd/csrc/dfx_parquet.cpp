@@ -9,6 +9,10 @@
 // (walk_chunk), and the kernels of dfx_k_parquet.hip turn the chunk into an Arrow column.  Chunks go one after the other: a chunk's
 // control block and counters are read back (one synchronisation) before the next chunk is read from the file.  A column nobody reads is neither read from the file nor copied: it is an `absent`
 // placeholder, as CsvRelation leaves unconverted columns.  Batches are zero-copy slices of the decoded row group.
+//
+// A chunk of codec 7 (LZ4_RAW) is inflated on the device first (inflate_chunk: header pass on the host, k_pq_inflate, the pages'
+// prologues read back, body pass on the host -- one synchronisation more per chunk); from the page table on it takes the same path,
+// the kernels reading the inflated image instead of the chunk.  An UNCOMPRESSED chunk pays nothing for that.
 #include <errno.h>
 #include <fcntl.h>
 #include <string.h>
@@ -61,6 +65,8 @@ class ParquetRelation : public Relation {
   bool is_needed(size_t c) const { return needed_.empty() || (c < needed_.size() && needed_[c]); }
   Status load_row_group();
   Status decode_chunk(size_t g, size_t c, DeviceColumn* col);
+  Status inflate_chunk(const uint8_t* host, size_t len, const uint8_t* dev_chunk, int32_t codec, const pq::Column& pc, int64_t rows, const std::string& where,
+                       std::shared_ptr<void>* image_out, pq::WalkedChunk* w);
   std::string filename_;
   int64_t batch_size_;
   int fd_ = -1;
@@ -77,6 +83,8 @@ class ParquetRelation : public Relation {
   int64_t pos_ = 0;       // ... rows handed out
   std::shared_ptr<void> stage_;  // pinned staging, as large as the largest chunk read so far
   size_t stage_bytes_ = 0;
+  std::shared_ptr<void> image_stage_;  // pinned: the inflated image of a compressed BYTE_ARRAY chunk, for the length chains
+  size_t image_stage_bytes_ = 0;
 };
 
 Status ParquetRelation::open(const int32_t* projection, int32_t n_projection) {
@@ -124,6 +132,15 @@ void ParquetRelation::explain(std::string* out, int depth) const {
   std::string line = strfmt("ParquetDataSource: %s, %d row groups, %d of %d column chunks read, decoded on the device", filename_.c_str(), (int)rgs,
                             (int)(n * rgs), (int)(cols_.size() * rgs));
   line += batch_size_ > 0 ? strfmt(", batches of %lld rows", (long long)((batch_size_ + 63) / 64 * 64)) : std::string(", one batch per row group");
+  // the codecs of the chunks read.  An UNCOMPRESSED chunk costs one host synchronisation; a compressed one two: its pages are
+  // inflated on the device and their prologues read back before the host can build the page table (inflate_chunk).
+  uint32_t codecs = 0;
+  for (size_t c = 0; c < proj_.size(); ++c)
+    for (const pq::RowGroupMeta& rg : meta_.row_groups)
+      if (is_needed(c) && rg.columns[(size_t)proj_[c]].codec >= 0 && rg.columns[(size_t)proj_[c]].codec < 8) codecs |= 1u << rg.columns[(size_t)proj_[c]].codec;
+  if (codecs) line += ", codecs:";
+  for (int k = 0; k < 8; ++k)
+    if (codecs & (1u << k)) line += std::string(" ") + pq::codec_name(k) + (k ? " (inflated on the device)" : "");
   for (size_t c = 0; c < proj_.size(); ++c) {
     if (!is_needed(c)) continue;
     uint32_t seen = 0;
@@ -165,7 +182,14 @@ Status ParquetRelation::decode_chunk(size_t g, size_t c, DeviceColumn* col) {
     ~SyncOnExit() { (void)hipStreamSynchronize(s); }
   } sync_on_exit{s};
   const std::string where = strfmt("column '%s', row group %d of %s", pc.name.c_str(), (int)g, filename_.c_str());
-  DFX_RETURN_IF_ERROR(from_pq(pq::walk_chunk(host, len, pc, rows, where, &w)));
+  if (km.codec == 0) {
+    DFX_RETURN_IF_ERROR(from_pq(pq::walk_chunk(host, len, pc, rows, where, &w)));
+  } else {
+    // a compressed chunk: the kernels below read the inflated image, and so does the body pass (one more synchronisation)
+    std::shared_ptr<void> image;
+    DFX_RETURN_IF_ERROR(inflate_chunk(host, len, (const uint8_t*)chunk.get(), km.codec, pc, rows, where, &image, &w));
+    chunk = image;
+  }
   counters().parquet_pages += (long long)w.infos.size();
   counters().parquet_dict_pages += w.dict_data_pages;
   counters().parquet_plain_pages += w.plain_pages;
@@ -283,6 +307,81 @@ Status ParquetRelation::decode_chunk(size_t g, size_t c, DeviceColumn* col) {
     col->validity = (const uint8_t*)validity.get();
     col->owners.push_back(validity);
   }
+  return Status::OK();
+}
+
+// A compressed chunk (codec 7, LZ4_RAW).  host / dev_chunk: the chunk's len bytes in the staging buffer and, once the copy in
+// flight on the stream has run, on the device.  The host's header pass sizes the inflated image and fills the inflate table while
+// that copy runs; k_pq_inflate inflates every page into the image; the pages' prologues and the control word come back (the first
+// of the chunk's two synchronisations), and the body pass builds the page table from them.  Only a BYTE_ARRAY chunk's image is
+// copied back to the host, for the length chains (parquet_inflated_bytes_to_host; a device walk of the chains would end that).
+Status ParquetRelation::inflate_chunk(const uint8_t* host, size_t len, const uint8_t* dev_chunk, int32_t codec, const pq::Column& pc, int64_t rows,
+                                      const std::string& where, std::shared_ptr<void>* image_out, pq::WalkedChunk* w) {
+  hipStream_t s = ctx().stream;
+  Status st;
+  std::vector<PqInflatePage> table;
+  std::vector<uint8_t> back;
+  struct SyncOnExit {  // the uploads read `table`, the copy back writes `back`: none is in flight when they go
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+  } sync_on_exit{s};
+  pq::ChunkHeaders hd;
+  DFX_RETURN_IF_ERROR(from_pq(pq::walk_headers(host, len, codec, pc, where, &hd)));
+  table = hd.table();
+  const size_t n = table.size();
+  const size_t image_bytes = (size_t)hd.image_len + 64;
+  auto image = device_alloc(image_bytes, &st);
+  if (!image) return st;
+  DFX_HIP(hipMemsetAsync(image.get(), 0, image_bytes, s));
+  auto dev_table = device_alloc(std::max<size_t>(sizeof(PqInflatePage) * n, 8), &st);
+  if (!dev_table) return st;
+  if (n) DFX_HIP(hipMemcpyAsync(dev_table.get(), table.data(), sizeof(PqInflatePage) * n, hipMemcpyHostToDevice, s));
+  // the control block, one word of statistics and the prologues: one zeroed buffer, one copy back
+  const size_t ctrl_bytes = sizeof(uint32_t) * CTRL_WORDS, back_bytes = ctrl_bytes + sizeof(uint64_t) + sizeof(PqPrologue) * n;
+  auto dev_back = device_alloc(back_bytes, &st);
+  if (!dev_back) return st;
+  DFX_HIP(hipMemsetAsync(dev_back.get(), 0, back_bytes, s));
+  DevPqInflate I;
+  memset(&I, 0, sizeof(I));
+  I.chunk = dev_chunk;
+  I.image = (uint8_t*)image.get();
+  I.pages = (const PqInflatePage*)dev_table.get();
+  I.n_pages = (uint32_t)n;
+  I.ctrl = (uint32_t*)dev_back.get();
+  I.stats = (uint64_t*)((uint8_t*)dev_back.get() + ctrl_bytes);
+  I.prologues = (PqPrologue*)((uint8_t*)dev_back.get() + ctrl_bytes + sizeof(uint64_t));
+  DFX_HIP(launch_pq_inflate(I, (double)hd.image_len, s));
+  back.resize(back_bytes);
+  DFX_HIP(hipMemcpyAsync(back.data(), dev_back.get(), back_bytes, hipMemcpyDeviceToHost, s));
+  const bool chains = pc.physical == pq::PT_BYTE_ARRAY;
+  if (chains) {
+    if (image_stage_bytes_ < image_bytes || !image_stage_) {
+      image_stage_.reset();
+      image_stage_ = pinned_alloc(image_bytes, &st);
+      if (!image_stage_) return st;
+      image_stage_bytes_ = image_bytes;
+    }
+    if (hd.image_len) DFX_HIP(hipMemcpyAsync(image_stage_.get(), image.get(), (size_t)hd.image_len, hipMemcpyDeviceToHost, s));
+    counters().parquet_inflated_bytes_to_host += (long long)hd.image_len;
+  }
+  DFX_HIP(hipStreamSynchronize(s));
+  uint32_t ctrl_error = 0;
+  uint64_t sequences = 0;
+  memcpy(&ctrl_error, back.data() + sizeof(uint32_t) * CTRL_ERROR, sizeof(ctrl_error));
+  memcpy(&sequences, back.data() + ctrl_bytes, sizeof(sequences));
+  if (ctrl_error & PQ_ERR_ALL) {
+    Status err = error_from_ctrl(ctrl_error & PQ_ERR_ALL);
+    err.msg += " (" + where + ")";
+    return err;
+  }
+  counters().parquet_inflated_pages += hd.inflated_pages;
+  counters().parquet_stored_pages += hd.stored_pages;
+  counters().parquet_inflated_bytes += hd.inflated_bytes;
+  counters().parquet_lz4_sequences += (long long)sequences;
+  std::vector<PqPrologue> prologues(n);
+  if (n) memcpy(prologues.data(), back.data() + ctrl_bytes + sizeof(uint64_t), sizeof(PqPrologue) * n);
+  DFX_RETURN_IF_ERROR(from_pq(pq::walk_bodies(hd, chains ? (const uint8_t*)image_stage_.get() : nullptr, prologues.data(), pc, rows, where, w)));
+  *image_out = image;
   return Status::OK();
 }
 

@@ -1,7 +1,10 @@
 // dfx_parquet_meta.hpp -- the host side of the Parquet source (deviation D12), free of HIP: a bounds-checked reader of thrift's
 // compact protocol, FileMetaData / PageHeader, the supported subset, the walk over a column chunk's pages that fills the page
-// table (dfx_parquet_rle.hpp: PqPage) and the length chains of PLAIN byte arrays, and a sequential decoder of a whole chunk.
-// dfx_parquet.cpp uses everything but the decoder; tests/native/parquet_check.cpp holds all of it against pyarrow on the CPU.
+// table (dfx_parquet_rle.hpp: PqPage) and the length chains of PLAIN byte arrays, and a sequential decoder of a whole chunk.  For a
+// compressed chunk (codec 7, LZ4_RAW) the walk is split: a header pass over the file's bytes (walk_headers: the inflate table and
+// the layout of the inflated image), the inflate stage (dfx_parquet_lz4.hpp; on the device k_pq_inflate), a body pass over the image
+// or over the pages' prologues (walk_bodies).  dfx_parquet.cpp uses everything but the decoders; tests/native/parquet_check.cpp and
+// tests/native/parquet_lz4_check.cpp hold all of it against pyarrow on the CPU.
 //
 // Nothing here trusts a count from the file: lists are read element by element after their size has been checked against the
 // bytes that remain (an element takes at least one), extents are checked before they are used, and every failure is a
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "../../include/dfx.h"
+#include "dfx_parquet_lz4.hpp"
 #include "dfx_parquet_rle.hpp"
 
 namespace dfx {
@@ -476,10 +480,11 @@ inline Err resolve(const FileMeta& m, uint64_t file_size, uint32_t footer_len, s
       if (!k.has_meta) return parser_error(where + ": the chunk's metadata lacks a required field");
       if (k.type != (*cols)[c].physical) return parser_error(where + ": the chunk is of type " + std::string(physical_name(k.type)) + ", the schema says " + physical_name((*cols)[c].physical));
       if (k.path.size() != 1 || k.path[0] != (*cols)[c].name) return parser_error(where + ": the chunk's path in the schema is not the column's name");
-      if (k.codec != 0) return not_implemented(where + ": codec " + codec_name(k.codec) + " (only UNCOMPRESSED chunks are read: there is no decompressor on the device)");
+      if (k.codec != 0 && k.codec != 7)
+        return not_implemented(where + ": codec " + codec_name(k.codec) + " (only UNCOMPRESSED and LZ4_RAW chunks are read: the device has no other decompressor)");
       for (int32_t e : k.encodings)
         if (e != 0 && e != 2 && e != 3 && e != 4 && e != 8) return not_implemented(where + ": encoding " + std::string(encoding_name(e)) + " (" + num(e) + ")");
-      if (k.total_uncompressed_size != k.total_compressed_size) return parser_error(where + ": sizes " + num(k.total_uncompressed_size) + " / " + num(k.total_compressed_size) + " differ in an UNCOMPRESSED chunk");
+      if (k.codec == 0 && k.total_uncompressed_size != k.total_compressed_size) return parser_error(where + ": sizes " + num(k.total_uncompressed_size) + " / " + num(k.total_compressed_size) + " differ in an UNCOMPRESSED chunk");
       if (k.num_values != rg.num_rows) return parser_error(where + ": " + num(k.num_values) + " values in a row group of " + num(rg.num_rows) + " rows");
       if (k.dictionary_page_offset < 0 || k.data_page_offset < 0) return parser_error(where + ": a negative page offset");
       const int64_t s = k.start();
@@ -487,6 +492,9 @@ inline Err resolve(const FileMeta& m, uint64_t file_size, uint32_t footer_len, s
       if (s < 4 || k.total_compressed_size < 0 || (uint64_t)s > data_end || (uint64_t)k.total_compressed_size > data_end - (uint64_t)s)
         return parser_error(where + ": the chunk's extent [" + num(s) + ", +" + num(k.total_compressed_size) + ") is beyond the file's data");
       if (k.total_compressed_size >= (int64_t)0x7FFFFFFF) return not_implemented(where + ": a column chunk of 2 GB or more");
+      // (offsets into the inflated image of a compressed chunk are 32-bit as well: PqPage, PqInflatePage)
+      if (k.codec == 7 && (k.total_uncompressed_size < 0 || k.total_uncompressed_size >= (int64_t)0x7FFFFFFF))
+        return not_implemented(where + ": a column chunk of 2 GB or more");
     }
   }
   if (rows != m.num_rows) return parser_error("the row groups hold " + num(rows) + " rows, the file says " + num(m.num_rows));
@@ -499,6 +507,7 @@ struct PageHeader {
   int32_t uncompressed_size = -1, compressed_size = -1;
   int32_t num_values = -1, encoding = -1, def_encoding = -1;
   int32_t def_len = 0, rep_len = 0;  // V2
+  bool is_compressed = true;         // V2: the bytes after the levels are compressed (a chunk with a codec; the levels never are)
   size_t header_len = 0;
 };
 inline void read_sub_header(Thrift& t, int kind, PageHeader* h) {
@@ -510,7 +519,8 @@ inline void read_sub_header(Thrift& t, int kind, PageHeader* h) {
     else if (kind == 3 && id == 4 && ty == T_I32) h->encoding = t.i32();
     else if (kind == 3 && id == 5 && ty == T_I32) h->def_len = t.i32();
     else if (kind == 3 && id == 6 && ty == T_I32) h->rep_len = t.i32();
-    else t.skip(ty);  // statistics, is_sorted, is_compressed (the codec is UNCOMPRESSED), num_nulls, num_rows
+    else if (kind == 3 && id == 7 && (ty == T_TRUE || ty == T_FALSE)) h->is_compressed = t.boolean(ty);
+    else t.skip(ty);  // statistics, is_sorted, num_nulls, num_rows
   }
 }
 inline bool parse_page_header(const uint8_t* p, size_t n, PageHeader* h) {
@@ -563,14 +573,149 @@ inline bool walk_length_chain(const uint8_t* chunk, uint32_t off, uint32_t len, 
   return true;
 }
 
-// chunk: the chunk's len bytes (len < 2^31).  where: "column 'x', row group g" for the messages.
+// The bytes a page's body is read from.  The body pass reads little of a body: the 4-byte length of a V1 page's definition levels,
+// the index width byte, the 4-byte length of RLE Booleans, and the length chains of BYTE_ARRAY values.  For an uncompressed chunk
+// `base` is the chunk; for a compressed one it is the inflated image where the host has it (BYTE_ARRAY chunks), and null where
+// only the page's prologue came back from the device (dfx_parquet_lz4.hpp: PqPrologue), which holds the first three.
+struct PageBytes {
+  const uint8_t* base = nullptr;
+  uint32_t body = 0;  // the page's body within `base`
+  PqPrologue pro{0, 0};
+  uint64_t probe_off = 0;  // body offset of pro.probe
+  bool le32(uint32_t off, uint32_t* v) const {
+    if (base) *v = (uint32_t)base[off] | (uint32_t)base[off + 1] << 8 | (uint32_t)base[off + 2] << 16 | (uint32_t)base[off + 3] << 24;
+    else if (off == body) *v = pro.word0;
+    else if ((uint64_t)off == (uint64_t)body + probe_off) *v = pro.probe;
+    else return false;
+    return true;
+  }
+};
+inline std::string page_where(const std::string& where, int page_no, size_t pos) {
+  return where + ", page " + num(page_no) + " at byte " + num((long long)pos) + " of the chunk";
+}
+
+// The body pass of one page: the page's entry in the page table, its offsets relative to b.base's first byte.  [body, body + size)
+// is the page's uncompressed body and lies inside what b.base points to.  rows: the rows of the pages before it, updated.
+inline Err walk_page(const PageHeader& h, const std::string& pw, const PageBytes& b, uint32_t body, uint32_t size, const Column& col, int64_t rg_rows,
+                     int64_t* rows_io, WalkedChunk* w) {
+  const int width = physical_width(col.physical);
+  const int64_t rows = *rows_io;
+  auto unread = [&] { return parser_error(pw + ": the body pass asks for bytes of the page that were not read back"); };
+  if (h.type == 1) return Err();  // index page: skipped, never interpreted
+  if (h.type != 0 && h.type != 2 && h.type != 3) return parser_error(pw + ": page type " + num(h.type));
+  if (h.num_values < 0) return parser_error(pw + ": " + num(h.num_values) + " values");
+  PageInfo info;
+  info.kind = h.type;
+  info.encoding = h.encoding;
+  info.num_values = h.num_values;
+  w->infos.push_back(info);
+  if (h.type == 2) {
+    if (w->has_dict || !w->pages.empty()) return parser_error(pw + ": a dictionary page that is not the chunk's first page");
+    if (h.encoding != 0 && h.encoding != 2) return not_implemented(pw + ": dictionary page encoded " + std::string(encoding_name(h.encoding)));
+    if (col.physical == PT_BOOLEAN) return parser_error(pw + ": a dictionary page in a BOOLEAN chunk");
+    w->has_dict = true;
+    w->dict_off = body;
+    w->dict_len = size;
+    w->dict_n = (uint32_t)h.num_values;
+    if (col.physical == PT_BYTE_ARRAY) {
+      uint32_t n = 0;
+      if (!b.base) return unread();
+      if (!walk_length_chain(b.base, body, size, (uint64_t)h.num_values, false, &w->dict_str, &n))
+        return parser_error(pw + ": a string length of the dictionary overruns its page");
+      w->walked_strings += n;
+    } else if ((uint64_t)h.num_values * (uint64_t)width > size) {
+      return parser_error(pw + ": " + num(h.num_values) + " dictionary values overrun the page's " + num(size) + " bytes");
+    }
+    ++w->dict_pages;
+    return Err();
+  }
+  if ((int64_t)h.num_values > rg_rows - rows) return parser_error(pw + ": page value counts exceed the row group's " + num(rg_rows) + " rows");
+  PqPage p;
+  memset(&p, 0, sizeof(p));
+  p.num_values = (uint32_t)h.num_values;
+  p.first_row = (uint32_t)rows;
+  p.dense_base = w->dense_total;
+  p.rank_base = w->rank_total;
+  uint32_t voff = body, vlen = size;
+  if (h.type == 0) {
+    if (col.optional) {
+      if (h.def_encoding != 3) return not_implemented(pw + ": definition levels encoded " + std::string(encoding_name(h.def_encoding)));
+      if (vlen < 4) return parser_error(pw + ": no room for the length of the definition levels");
+      uint32_t l = 0;
+      if (!b.le32(voff, &l)) return unread();
+      if (l > vlen - 4) return parser_error(pw + ": the definition levels' " + num(l) + " bytes overrun the page");
+      p.lev_off = voff + 4;
+      p.lev_len = l;
+      voff += 4 + l;
+      vlen -= 4 + l;
+    }
+  } else {
+    if (h.rep_len != 0) return not_implemented(pw + ": repetition levels in a flat column");
+    if (h.def_len < 0 || (uint32_t)h.def_len > vlen) return parser_error(pw + ": the definition levels' " + num(h.def_len) + " bytes overrun the page");
+    if (col.optional) {
+      p.lev_off = voff;
+      p.lev_len = (uint32_t)h.def_len;
+    }
+    voff += (uint32_t)h.def_len;
+    vlen -= (uint32_t)h.def_len;
+  }
+  if (h.encoding == 0) {
+    p.enc = PQ_ENC_PLAIN;
+    if (col.physical == PT_BYTE_ARRAY) {
+      p.str_base = (uint32_t)w->str_offs.size();
+      uint32_t n = 0;
+      if (!b.base) return unread();
+      if (!walk_length_chain(b.base, voff, vlen, (uint64_t)h.num_values, true, &w->str_offs, &n))
+        return parser_error(pw + ": a string length overruns its page");
+      p.pad = n;  // strings the page holds
+      w->walked_strings += n;
+    }
+    ++w->plain_pages;
+  } else if (h.encoding == 2 || h.encoding == 8) {
+    if (!w->has_dict) return parser_error(pw + ": dictionary-encoded values without a dictionary page");
+    if (vlen < 1) return parser_error(pw + ": no room for the bit width of the dictionary indices");
+    p.enc = PQ_ENC_DICT;
+    ++w->dict_data_pages;
+    uint32_t first = 0;  // (the width byte is the low byte of the word at voff; a page that ends inside the word is read to its end)
+    if (b.base) first = b.base[voff];
+    else if (!b.le32(voff, &first)) return unread();
+    p.bit_width = first & 0xFFu;
+    if (p.bit_width > 32) return parser_error(pw + ": dictionary indices of " + num(p.bit_width) + " bits");
+    voff += 1;
+    vlen -= 1;
+  } else if (h.encoding == 3 && col.physical == PT_BOOLEAN) {
+    if (vlen < 4) return parser_error(pw + ": no room for the length of the RLE values");
+    uint32_t l = 0;
+    if (!b.le32(voff, &l)) return unread();
+    if (l > vlen - 4) return parser_error(pw + ": the RLE values' " + num(l) + " bytes overrun the page");
+    p.enc = PQ_ENC_RLE_BOOL;
+    voff += 4;
+    vlen = l;
+  } else {
+    return not_implemented(pw + ": values encoded " + std::string(encoding_name(h.encoding)) + " (" + num(h.encoding) + ")");
+  }
+  p.val_off = voff;
+  p.val_len = vlen;
+  w->encodings_seen |= 1u << p.enc;
+  *rows_io = rows + h.num_values;
+  w->dense_total += p.num_values;
+  w->rank_total += (uint32_t)(((uint64_t)p.first_row + p.num_values + 63) / 64 - p.first_row / 64) + 1;
+  w->pages.push_back(p);
+  return Err();
+}
+inline Err rows_error(int64_t rows, int64_t rg_rows, const std::string& where) {
+  if (rows != rg_rows) return parser_error(where + ": the pages hold " + num(rows) + " values, the row group has " + num(rg_rows) + " rows");
+  return Err();
+}
+
+// An UNCOMPRESSED chunk: header and body of every page in one walk over the chunk's bytes, which are the bytes the page table points
+// into.  chunk: the chunk's len bytes (len < 2^31).  where: "column 'x', row group g" for the messages.
 inline Err walk_chunk(const uint8_t* chunk, size_t len, const Column& col, int64_t rg_rows, const std::string& where, WalkedChunk* w) {
   size_t pos = 0;
   int64_t rows = 0;
   int page_no = 0;
-  const int width = physical_width(col.physical);
   while (pos < len) {
-    const std::string pw = where + ", page " + num(page_no) + " at byte " + num((long long)pos) + " of the chunk";
+    const std::string pw = page_where(where, page_no, pos);
     PageHeader h;
     if (!parse_page_header(chunk + pos, len - pos, &h)) return parser_error(pw + ": the page header's thrift overruns the chunk");
     if (h.compressed_size < 0 || (size_t)h.compressed_size > len - pos - h.header_len)
@@ -579,102 +724,127 @@ inline Err walk_chunk(const uint8_t* chunk, size_t len, const Column& col, int64
     const uint32_t body = (uint32_t)(pos + h.header_len), size = (uint32_t)h.compressed_size;
     pos += h.header_len + size;
     ++page_no;
-    if (h.type == 1) continue;  // index page: skipped, never interpreted
-    if (h.type != 0 && h.type != 2 && h.type != 3) return parser_error(pw + ": page type " + num(h.type));
-    if (h.num_values < 0) return parser_error(pw + ": " + num(h.num_values) + " values");
-    PageInfo info;
-    info.kind = h.type;
-    info.encoding = h.encoding;
-    info.num_values = h.num_values;
-    w->infos.push_back(info);
-    if (h.type == 2) {
-      if (w->has_dict || !w->pages.empty()) return parser_error(pw + ": a dictionary page that is not the chunk's first page");
-      if (h.encoding != 0 && h.encoding != 2) return not_implemented(pw + ": dictionary page encoded " + std::string(encoding_name(h.encoding)));
-      if (col.physical == PT_BOOLEAN) return parser_error(pw + ": a dictionary page in a BOOLEAN chunk");
-      w->has_dict = true;
-      w->dict_off = body;
-      w->dict_len = size;
-      w->dict_n = (uint32_t)h.num_values;
-      if (col.physical == PT_BYTE_ARRAY) {
-        uint32_t n = 0;
-        if (!walk_length_chain(chunk, body, size, (uint64_t)h.num_values, false, &w->dict_str, &n))
-          return parser_error(pw + ": a string length of the dictionary overruns its page");
-        w->walked_strings += n;
-      } else if ((uint64_t)h.num_values * (uint64_t)width > size) {
-        return parser_error(pw + ": " + num(h.num_values) + " dictionary values overrun the page's " + num(size) + " bytes");
-      }
-      ++w->dict_pages;
-      continue;
-    }
-    if ((int64_t)h.num_values > rg_rows - rows) return parser_error(pw + ": page value counts exceed the row group's " + num(rg_rows) + " rows");
-    PqPage p;
-    memset(&p, 0, sizeof(p));
-    p.num_values = (uint32_t)h.num_values;
-    p.first_row = (uint32_t)rows;
-    p.dense_base = w->dense_total;
-    p.rank_base = w->rank_total;
-    uint32_t voff = body, vlen = size;
-    if (h.type == 0) {
-      if (col.optional) {
-        if (h.def_encoding != 3) return not_implemented(pw + ": definition levels encoded " + std::string(encoding_name(h.def_encoding)));
-        if (vlen < 4) return parser_error(pw + ": no room for the length of the definition levels");
-        const uint32_t l = (uint32_t)chunk[voff] | (uint32_t)chunk[voff + 1] << 8 | (uint32_t)chunk[voff + 2] << 16 | (uint32_t)chunk[voff + 3] << 24;
-        if (l > vlen - 4) return parser_error(pw + ": the definition levels' " + num(l) + " bytes overrun the page");
-        p.lev_off = voff + 4;
-        p.lev_len = l;
-        voff += 4 + l;
-        vlen -= 4 + l;
-      }
-    } else {
-      if (h.rep_len != 0) return not_implemented(pw + ": repetition levels in a flat column");
-      if (h.def_len < 0 || (uint32_t)h.def_len > vlen) return parser_error(pw + ": the definition levels' " + num(h.def_len) + " bytes overrun the page");
-      if (col.optional) {
-        p.lev_off = voff;
-        p.lev_len = (uint32_t)h.def_len;
-      }
-      voff += (uint32_t)h.def_len;
-      vlen -= (uint32_t)h.def_len;
-    }
-    if (h.encoding == 0) {
-      p.enc = PQ_ENC_PLAIN;
-      if (col.physical == PT_BYTE_ARRAY) {
-        p.str_base = (uint32_t)w->str_offs.size();
-        uint32_t n = 0;
-        if (!walk_length_chain(chunk, voff, vlen, (uint64_t)h.num_values, true, &w->str_offs, &n))
-          return parser_error(pw + ": a string length overruns its page");
-        p.pad = n;  // strings the page holds
-        w->walked_strings += n;
-      }
-      ++w->plain_pages;
-    } else if (h.encoding == 2 || h.encoding == 8) {
-      if (!w->has_dict) return parser_error(pw + ": dictionary-encoded values without a dictionary page");
-      if (vlen < 1) return parser_error(pw + ": no room for the bit width of the dictionary indices");
-      p.enc = PQ_ENC_DICT;
-      ++w->dict_data_pages;
-      p.bit_width = chunk[voff];
-      if (p.bit_width > 32) return parser_error(pw + ": dictionary indices of " + num(p.bit_width) + " bits");
-      voff += 1;
-      vlen -= 1;
-    } else if (h.encoding == 3 && col.physical == PT_BOOLEAN) {
-      if (vlen < 4) return parser_error(pw + ": no room for the length of the RLE values");
-      const uint32_t l = (uint32_t)chunk[voff] | (uint32_t)chunk[voff + 1] << 8 | (uint32_t)chunk[voff + 2] << 16 | (uint32_t)chunk[voff + 3] << 24;
-      if (l > vlen - 4) return parser_error(pw + ": the RLE values' " + num(l) + " bytes overrun the page");
-      p.enc = PQ_ENC_RLE_BOOL;
-      voff += 4;
-      vlen = l;
-    } else {
-      return not_implemented(pw + ": values encoded " + std::string(encoding_name(h.encoding)) + " (" + num(h.encoding) + ")");
-    }
-    p.val_off = voff;
-    p.val_len = vlen;
-    w->encodings_seen |= 1u << p.enc;
-    rows += h.num_values;
-    w->dense_total += p.num_values;
-    w->rank_total += (uint32_t)(((uint64_t)p.first_row + p.num_values + 63) / 64 - p.first_row / 64) + 1;
-    w->pages.push_back(p);
+    PageBytes b;
+    b.base = chunk;
+    b.body = body;
+    const Err e = walk_page(h, pw, b, body, size, col, rg_rows, &rows, w);
+    if (!e.ok()) return e;
   }
-  if (rows != rg_rows) return parser_error(where + ": the pages hold " + num(rows) + " values, the row group has " + num(rg_rows) + " rows");
+  return rows_error(rows, rg_rows, where);
+}
+
+// ---- a compressed chunk: the header pass, the inflated image, the body pass -----------------------------------------------------
+// The header pass needs the file's bytes only.  Per page (index pages are skipped) it keeps the parsed header and gives the page's
+// entry of the inflate table: where the body lies in the chunk, how much of it is V2's uncompressed level prefix, and where the body
+// goes in the INFLATED IMAGE, in which the bodies sit back to back, 8-byte aligned, the dictionary page first (it is the chunk's
+// first page).  Nothing is sized by a number from the file that has not been checked: an uncompressed size beyond what a block of
+// the compressed size can hold (an extension byte adds at most 255 bytes of output, so no valid LZ4 block exceeds 255 x its size
+// + 64) is refused here, before the image is allocated.
+struct HeaderPage {
+  PageHeader h;
+  int page_no = 0;
+  size_t pos = 0;  // of the header in the chunk
+  PqInflatePage ip;
+};
+struct ChunkHeaders {
+  std::vector<HeaderPage> pages;
+  uint64_t image_len = 0;
+  long long inflated_pages = 0, stored_pages = 0, inflated_bytes = 0;  // inflated_bytes: of image produced (V2 prefixes are copies)
+  long long oversized_v1_pages = 0;  // pages whose block is larger than what it inflates to (legal: the writer compresses anyway)
+  std::vector<PqInflatePage> table() const {
+    std::vector<PqInflatePage> t;
+    for (const HeaderPage& p : pages) t.push_back(p.ip);
+    return t;
+  }
+};
+inline Err walk_headers(const uint8_t* chunk, size_t len, int32_t codec, const Column& col, const std::string& where, ChunkHeaders* out) {
+  size_t pos = 0;
+  int page_no = 0;
+  while (pos < len) {
+    const std::string pw = page_where(where, page_no, pos);
+    HeaderPage hp;
+    PageHeader& h = hp.h;
+    if (!parse_page_header(chunk + pos, len - pos, &h)) return parser_error(pw + ": the page header's thrift overruns the chunk");
+    if (h.compressed_size < 0 || (size_t)h.compressed_size > len - pos - h.header_len)
+      return parser_error(pw + ": the page's " + num(h.compressed_size) + " bytes are beyond the chunk's extent");
+    hp.page_no = page_no;
+    hp.pos = pos;
+    const uint32_t body = (uint32_t)(pos + h.header_len);
+    pos += h.header_len + (size_t)h.compressed_size;
+    ++page_no;
+    if (h.type == 1) continue;  // index page: skipped, never interpreted, never inflated
+    if (h.type != 0 && h.type != 2 && h.type != 3) return parser_error(pw + ": page type " + num(h.type));
+    int64_t prefix = 0;
+    if (h.type == 3) {
+      if (h.rep_len < 0 || h.def_len < 0 || (int64_t)h.rep_len + h.def_len > (int64_t)h.compressed_size)
+        return parser_error(pw + ": the levels' " + num(h.rep_len) + " + " + num(h.def_len) + " bytes overrun the page");
+      prefix = (int64_t)h.rep_len + h.def_len;
+    }
+    if (h.uncompressed_size < 0 || (int64_t)h.uncompressed_size < prefix)
+      return parser_error(pw + ": an uncompressed size of " + num(h.uncompressed_size) + " bytes is below the levels' " + num(prefix));
+    const bool compressed = h.type != 3 || h.is_compressed;
+    if (compressed && (int64_t)h.uncompressed_size > 255ll * h.compressed_size + 64)
+      return parser_error(pw + ": an uncompressed size of " + num(h.uncompressed_size) + " bytes is more than a block of " + num(h.compressed_size) + " bytes can hold");
+    if (!compressed && h.uncompressed_size != h.compressed_size)
+      return parser_error(pw + ": sizes " + num(h.uncompressed_size) + " / " + num(h.compressed_size) + " differ in a page that is not compressed");
+    const uint64_t dst = (out->image_len + 7) & ~7ull;
+    if (dst + (uint64_t)h.uncompressed_size >= 0x7FFFFFFFull) return not_implemented(pw + ": the chunk's pages inflate to 2 GB or more");
+    memset(&hp.ip, 0, sizeof(hp.ip));
+    hp.ip.src_off = body;
+    hp.ip.src_len = (uint32_t)h.compressed_size;
+    hp.ip.dst_off = (uint32_t)dst;
+    hp.ip.dst_len = (uint32_t)h.uncompressed_size;
+    hp.ip.prefix_len = (uint32_t)prefix;
+    hp.ip.flags = compressed ? PQ_INFLATE_COMPRESSED : 0u;
+    hp.ip.codec = (uint32_t)codec;
+    if (h.type == 0 && col.optional) hp.ip.flags |= PQ_INFLATE_PROBE_AFTER_LEVELS;  // the values follow the level block
+    if (h.type == 3) hp.ip.probe_off = (uint32_t)h.def_len;                          // ... the (uncompressed) levels
+    out->image_len = dst + (uint64_t)h.uncompressed_size;
+    if (compressed) ++out->inflated_pages; else ++out->stored_pages;
+    out->inflated_bytes += (long long)h.uncompressed_size - prefix;
+    if (h.type != 3 && h.compressed_size > h.uncompressed_size) ++out->oversized_v1_pages;
+    out->pages.push_back(hp);
+  }
   return Err();
+}
+
+// the inflate stage on the host, page by page as the kernel does it: prefix and stored pages are copies.  image: image_len bytes,
+// zeroed.  false: the page's block is malformed (PQ_ERR_INFLATE).
+inline bool inflate_page(const uint8_t* chunk, const PqInflatePage& ip, uint8_t* image, Lz4Stats* stats) {
+  memcpy(image + ip.dst_off, chunk + ip.src_off, ip.prefix_len);
+  const uint8_t* src = chunk + ip.src_off + ip.prefix_len;
+  uint8_t* dst = image + ip.dst_off + ip.prefix_len;
+  const uint32_t src_len = ip.src_len - ip.prefix_len, dst_len = ip.dst_len - ip.prefix_len;
+  if (!(ip.flags & PQ_INFLATE_COMPRESSED)) {
+    memcpy(dst, src, dst_len);  // (== src_len: walk_headers)
+    if (stats) ++stats->stored_pages;
+    return true;
+  }
+  return lz4_decode_block(src, src_len, dst, dst_len, stats);
+}
+inline PqPrologue page_prologue(const uint8_t* image, const PqInflatePage& ip) {
+  PqPrologue p;
+  p.word0 = pq_le32_or_zero(image + ip.dst_off, ip.dst_len, 0);
+  p.probe = pq_le32_or_zero(image + ip.dst_off, ip.dst_len, pq_probe_offset(ip, p.word0));
+  return p;
+}
+
+// The body pass: the same page table, checks and messages as walk_chunk's, the offsets pointing into the inflated image.  image:
+// the image's bytes, or null where only the prologues (one per page of hd) are known: enough for fixed-width and Boolean chunks.
+inline Err walk_bodies(const ChunkHeaders& hd, const uint8_t* image, const PqPrologue* prologues, const Column& col, int64_t rg_rows, const std::string& where,
+                       WalkedChunk* w) {
+  int64_t rows = 0;
+  for (size_t i = 0; i < hd.pages.size(); ++i) {
+    const HeaderPage& hp = hd.pages[i];
+    PageBytes b;
+    b.base = image;
+    b.body = hp.ip.dst_off;
+    b.pro = prologues[i];
+    b.probe_off = pq_probe_offset(hp.ip, b.pro.word0);
+    const Err e = walk_page(hp.h, page_where(where, hp.page_no, hp.pos), b, hp.ip.dst_off, hp.ip.dst_len, col, rg_rows, &rows, w);
+    if (!e.ok()) return e;
+  }
+  return rows_error(rows, rg_rows, where);
 }
 
 // The bytes of a Utf8 column of one row group must fit Arrow's 32-bit offsets.  The sum is NOT bounded by the chunk: the rows of a

@@ -26,7 +26,8 @@ enum : uint32_t {
   PQ_ERR_RUN = 1u << 16,         // a run of a hybrid stream overruns its page (or its header is malformed)
   PQ_ERR_DICT_INDEX = 1u << 17,  // a dictionary index >= the dictionary's size
   PQ_ERR_VALUE = 1u << 18,       // a page holds fewer values than its levels say are non-null
-  PQ_ERR_ALL = PQ_ERR_RUN | PQ_ERR_DICT_INDEX | PQ_ERR_VALUE
+  PQ_ERR_INFLATE = 1u << 19,     // a compressed page's block is malformed (dfx_parquet_lz4.hpp: the bounds rules)
+  PQ_ERR_ALL = PQ_ERR_RUN | PQ_ERR_DICT_INDEX | PQ_ERR_VALUE | PQ_ERR_INFLATE
 };
 
 enum : uint32_t { PQ_ENC_PLAIN = 0, PQ_ENC_DICT = 1, PQ_ENC_RLE_BOOL = 2 };

@@ -10,6 +10,7 @@ Status error_from_ctrl(uint32_t bits) {
   if (bits & 2u) return Status::Err(DFX_INTERNAL_ERROR, "attempt to divide with overflow");
   if (bits & 4u) return Status::Err(DFX_INTERNAL_ERROR, "partitioned aggregation: LDS ring stalled");
   if (bits & 8u) return Status::Err(DFX_INTERNAL_ERROR, "single-pass filter: look-back stalled");
+  if (bits & PQ_ERR_INFLATE) return Status::Err(DFX_PARSER_ERROR, "Parquet: the compressed block of a page is malformed");
   if (bits & PQ_ERR_RUN) return Status::Err(DFX_PARSER_ERROR, "Parquet: a run of a page's levels or values overruns the page");
   if (bits & PQ_ERR_DICT_INDEX) return Status::Err(DFX_PARSER_ERROR, "Parquet: a dictionary index is beyond the dictionary");
   if (bits & PQ_ERR_VALUE) return Status::Err(DFX_PARSER_ERROR, "Parquet: a page holds fewer values than its non-null rows");

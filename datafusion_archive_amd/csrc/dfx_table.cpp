@@ -515,6 +515,11 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "parquet_rle_runs")) return counters().parquet_rle_runs;
   if (!strcmp(name, "parquet_bitpacked_runs")) return counters().parquet_bitpacked_runs;
   if (!strcmp(name, "parquet_host_walked_strings")) return counters().parquet_host_walked_strings;
+  if (!strcmp(name, "parquet_inflated_pages")) return counters().parquet_inflated_pages;
+  if (!strcmp(name, "parquet_stored_pages")) return counters().parquet_stored_pages;
+  if (!strcmp(name, "parquet_inflated_bytes")) return counters().parquet_inflated_bytes;
+  if (!strcmp(name, "parquet_lz4_sequences")) return counters().parquet_lz4_sequences;
+  if (!strcmp(name, "parquet_inflated_bytes_to_host")) return counters().parquet_inflated_bytes_to_host;
   if (!strcmp(name, "xchg_calls")) return counters().xchg_calls;
   if (!strcmp(name, "xchg_local_us")) return counters().xchg_local_us;
   if (!strcmp(name, "xchg_wait_peers_us")) return counters().xchg_wait_peers_us;

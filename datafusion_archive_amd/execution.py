@@ -215,7 +215,7 @@ class ParquetDataSource(Relation):
     """DataSourceMeta::ParquetFile { filename, schema, projection } (datasource.rs:87-92), which the reference declares and never
     executes (deviation D12).  The schema comes from the file; `projection` is a list of leaf-column indices (None: all, in file
     order); `batch_size` <= 0 gives one batch per row group, otherwise slices of batch_size rows rounded up to a multiple of 64.
-    Uncompressed column chunks are decoded on the device; a consumer's projection push-down keeps the chunks of unread columns
+    UNCOMPRESSED or LZ4_RAW column chunks are decoded on the device (LZ4_RAW pages are inflated there first); a consumer's projection push-down keeps the chunks of unread columns
     on disk."""
 
     def __init__(self, filename: str, projection: Optional[Sequence[int]] = None, batch_size: int = 0):

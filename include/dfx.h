@@ -347,13 +347,13 @@ int32_t dfx_csv_datasource_new(const char* filename, const struct ArrowSchema* s
  *               batch_size <= 0: one batch per row group; > 0: zero-copy slices of batch_size rows rounded up to a multiple of
  *               64, the last of a row group short.  A batch never spans row groups; a row group of 0 rows yields none.
  *   subset      flat schemas (required / optional leaves under the root); BOOLEAN, INT32 (+ Int(8/16/32, s/u) by truncation), INT64
- *               (+ Int(64, s/u)), FLOAT, DOUBLE, BYTE_ARRAY annotated String; codec UNCOMPRESSED only (there is no decompressor on
- *               the device); dictionary pages, data pages V1 and V2; PLAIN, RLE_DICTIONARY / PLAIN_DICTIONARY, RLE Booleans; a chunk
+ *               (+ Int(64, s/u)), FLOAT, DOUBLE, BYTE_ARRAY annotated String; codec UNCOMPRESSED or LZ4_RAW (codec 7; its pages are
+ *               inflated on the device); dictionary pages, data pages V1 and V2; PLAIN, RLE_DICTIONARY / PLAIN_DICTIONARY, RLE Booleans; a chunk
  *               that falls back from its dictionary to PLAIN pages.  Anything else is DFX_NOT_IMPLEMENTED at construction, naming
  *               the column and the thing -- also for a column the projection leaves out: the subset is a property of the file.
  *   errors      a missing or unreadable file is DFX_IO_ERROR; a file that is not Parquet or is damaged (magic, footer length,
  *               thrift overrunning its buffer, extents beyond the file or chunk, value counts that do not add up, a run overrunning
- *               its page, a dictionary index beyond the dictionary, a string length overrunning its page) is DFX_PARSER_ERROR
+ *               its page, a malformed compressed block, a dictionary index beyond the dictionary, a string length overrunning its page) is DFX_PARSER_ERROR
  *               saying what and where; no device is DFX_EXECUTION_ERROR (there is no host decoding path).
  * The stream is a library stream: operators stacked on it never leave the device.
  * ---------------------------------------------------------------------------------------- */

@@ -625,7 +625,7 @@ impl GpuRelation {
         Self::from_stream(out, schema)
     }
     /// DataSourceMeta::ParquetFile { filename, schema, projection } (datasource.rs:87-92; the reference has no executor): a leaf that
-    /// decodes uncompressed column chunks on the GPU.  `schema` is the one the meta carries (the library serves the file's own: it
+    /// decodes UNCOMPRESSED or LZ4_RAW column chunks on the GPU.  `schema` is the one the meta carries (the library serves the file's own: it
     /// must describe the projected columns); batch_size 0: one batch per row group
     pub fn parquet(filename: &str, schema: Arc<Schema>, projection: Option<Vec<usize>>, batch_size: usize) -> Result<Self> {
         let (mut out, mut err) = (Self::new_out(), [0 as c_char; ERRLEN]);
