@@ -110,8 +110,10 @@ def check_pass2_reserved_registers(asm: str) -> int:
     for k, body in kernels.items():
         if k not in meta:
             raise RuntimeError(f"build guard: no metadata for {k}")
-        used = max(_asm_registers(body) & reserved, default=0)  # v118 with 12-byte rows (dwordx3 loads), v119 with 16-byte rows
-        if used < 118:
+        # v117 with 8-byte rows (dwordx2 loads: the rows of two shadows), v118 with 12-byte rows (dwordx3), v119 with 16-byte rows
+        used = max(_asm_registers(body) & reserved, default=0)
+        widths = {int(m.group(1)) for m in re.finditer(r"\bglobal_load_dwordx([234])\s+v\[(?:8[89]|9\d|1[01]\d):", body)}
+        if not widths or used < 115 + max(widths):
             raise RuntimeError(f"build guard: {k}: the in-flight row registers v88..v119 are gone")
         if meta[k] <= used:
             raise RuntimeError(f"build guard: {k}: .vgpr_count = {meta[k]} does not cover v{used} (the in-flight row registers v88..v{used}): "
@@ -124,7 +126,7 @@ def check_pass2_reserved_registers(asm: str) -> int:
             ops = [o.strip() for o in rest.split(",")]
             if not (_asm_registers(rest) & reserved):
                 continue
-            if op in ("global_load_dwordx3", "global_load_dwordx4"):
+            if op in ("global_load_dwordx2", "global_load_dwordx3", "global_load_dwordx4"):
                 ok = _asm_registers(ops[0]) <= reserved and not (_asm_registers(",".join(ops[1:])) & reserved)
             elif op in ("v_mov_b32", "v_mov_b32_e32"):
                 ok = not (_asm_registers(ops[0]) & reserved) and _asm_registers(ops[1]) <= reserved

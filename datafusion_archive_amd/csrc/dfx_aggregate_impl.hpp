@@ -307,7 +307,9 @@ struct AggregateRelation::Impl {
   Status alloc_table(int cap_log2, DevTable* T, std::vector<std::shared_ptr<void>>* owners, bool new_ctrl, uint64_t** full_accs_out);
   void replace_table(const DevTable& Tn, uint64_t* accs_full_new, const std::vector<std::shared_ptr<void>>& owners, bool forget_snapshot);
   Status ensure_spill(int64_t rows);
-  Status ensure_partition(int64_t rows, bool nulls_now = false);
+  // both_shadows: every launch these regions are sized for binds both column shadows (launch_rows: both_shadows_bind)
+  Status ensure_partition(int64_t rows, bool nulls_now = false, bool both_shadows = false);
+  RoutedLayoutQuery layout_query(int64_t rows, bool nulls_now, bool both_shadows) const;
   bool shared_operand() const;
   Status flush_pass2();
   uint64_t program_fingerprint() const;
@@ -327,6 +329,14 @@ struct AggregateRelation::Impl {
   size_t shadow_query_bytes() const;  // the memory rule's "what this query holds"
   bool value_shadow_asked = false;
   int64_t value_shadow_launches = 0;  // (explain)
+  // The routed row form (agg.routed_row8): would a launch of this bound batch bind BOTH shadows -- each eligible and already built?
+  // Asked before ensure_partition, without side effects: nothing is counted, nothing is built.  A query that builds a shadow
+  // itself keeps its 12-byte rows to the end (shadow_built_here).
+  int key_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const;    // -1: not this launch
+  int value_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const;  // -1: not this launch
+  bool both_shadows_bind(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t rows, int64_t row0);
+  bool shadow_built_here = false;
+  int64_t row8_launches = 0;  // (explain)
   Status drain();
   Status emit_grouped(DeviceBatch* out, int64_t expected);
   std::shared_ptr<void> emit_total;  // pinned: the scan's group count

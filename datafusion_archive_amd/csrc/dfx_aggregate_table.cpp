@@ -88,9 +88,8 @@ bool AggregateRelation::Impl::shared_operand() const {
   return true;
 }
 
-// scratch for the partitioned strategy, sized for a batch of `rows` rows (worst case: all pass).  The policy -- which pass-1 flavour
-// routes the rows, the row form, the regions' geometry -- is choose_routed_layout (dfx_pass1_layout.hpp)
-Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now) {
+// what choose_routed_layout (dfx_pass1_layout.hpp) is asked for a batch of `rows` rows; both_shadows: launch_rows' both_shadows_bind
+RoutedLayoutQuery AggregateRelation::Impl::layout_query(int64_t rows, bool nulls_now, bool both_shadows) const {
   RoutedLayoutQuery q = {};
   q.rows = rows, q.nulls_now = nulls_now, q.kw = kw, q.na = na();
   q.table_slots = T.mask + 1, q.block_slots = (uint64_t)T.block_mask + 1, q.cu_count = device_cu_count();
@@ -100,9 +99,16 @@ Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now) {
   q.has_pred = has_pred, q.unfused_now = unfused_now;
   q.narrow = dec.narrow, q.dense_seen = dec.dense_seen, q.mostly_seen = dec.mostly_seen, q.skew_seen = dec.skew_seen;
   q.opt = layout_options();
-  const RoutedLayout L = choose_routed_layout(q);
+  q.both_shadows = both_shadows && opt().routed_row8 != 0;
+  return q;
+}
+
+// scratch for the partitioned strategy, sized for a batch of `rows` rows (worst case: all pass).  The policy -- which pass-1 flavour
+// routes the rows, the row form, the regions' geometry -- is choose_routed_layout (dfx_pass1_layout.hpp)
+Status AggregateRelation::Impl::ensure_partition(int64_t rows, bool nulls_now, bool both_shadows) {
+  const RoutedLayout L = choose_routed_layout(layout_query(rows, nulls_now, both_shadows));
   if (L.kind == RoutedLayoutKind::refused_pair_scan) return Status::Err(DFX_NOT_IMPLEMENTED, "pair scan: not for this table");
-  const uint32_t form = PTF_NARROW | PTF_SHARED | PTF_PAIR | PTF_PLANES;
+  const uint32_t form = PTF_NARROW | PTF_SHARED | PTF_PAIR | PTF_PLANES | PTF_ROW8;  // (pass 2 reads a window in ONE row form)
   if (win.layout_valid && rows <= win.layout_rows && PT.n_parts == L.PT.n_parts && PT.n_words == L.PT.n_words && (PT.flags & form) == L.want_flags)
     return Status::OK();  // same table, a batch the regions were sized for: keep appending
   DFX_RETURN_IF_ERROR(flush_pass2());  // rows routed under the old layout
@@ -391,12 +397,19 @@ size_t AggregateRelation::Impl::shadow_query_bytes() const {
   return win.rows_bytes + win.cnt_bytes + (size_t)spill.capacity * 8 * (size_t)(kw + widest) + ((size_t)T.mask + 2) * 8 * (size_t)(kw + widest);
 }
 
+int AggregateRelation::Impl::key_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const {
+  const AggOptions& o = opt();
+  if (o.key_shadow == 0 || calibrating || !dec.narrow || kw != 1 || !fp.valid || prog.has_nulls || !input) return -1;
+  const int ks = fp.keycol[0];
+  if (ks >= prog.n_cols || prog.col_dtype[ks] != T_I64 || cols.c[ks].validity) return -1;
+  if (!partition_key_shadow_supported(prog, fp, cols, T, pt)) return -1;  // (no pass-1 kernel reads this shape's key from 4-byte words)
+  return ks;
+}
+
 const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) {
   const AggOptions& o = opt();
-  if (o.key_shadow == 0 || calibrating || !dec.narrow || kw != 1 || !fp.valid || prog.has_nulls || !input) return nullptr;
-  const int ks = fp.keycol[0];
-  if (ks >= prog.n_cols || prog.col_dtype[ks] != T_I64 || cols.c[ks].validity) return nullptr;
-  if (!partition_key_shadow_supported(prog, fp, cols, T, pt)) return nullptr;  // (no pass-1 kernel reads this shape's key from 4-byte words)
+  const int ks = key_shadow_column(prog, fp, cols, pt);
+  if (ks < 0) return nullptr;
   ScanMemo* memo = input->column_memo();
   if (!memo) return nullptr;
   const KeyShadowDevice dev = shadow_device(ctx().stream, launch_narrow_keys, &counters().agg_key_shadow_build_us);
@@ -404,18 +417,25 @@ const uint32_t* AggregateRelation::Impl::key_shadow_words(const DevProgram& prog
   key_shadow_asked = true;
   bool built = false;
   const uint32_t* words = memo->key_shadows.acquire(cols.c[ks].values, o.key_shadow, first, shadow_query_bytes(), dev, &built);
-  if (built) ++counters().agg_key_shadow_builds;
+  if (built) ++counters().agg_key_shadow_builds, shadow_built_here = true;
   return words;
 }
 
 // prog, pt: the launch with the key shadow bound; cols: the batch as the operator bound it (before row0).  The kernels' own
 // condition (partition_value_shadow_supported: one of the two signatures -- the operand a plain Float64 column, every predicate
 // term on it, SUM or the shared raw operand) and the operator's: no nulls, no calibration slice, a resident table below.
+int AggregateRelation::Impl::value_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const {
+  const AggOptions& o = opt();
+  if (o.value_shadow == 0 || calibrating || !(pt.flags & PTF_KEY4) || prog.has_nulls || !input) return -1;
+  int vc = 0;
+  if (!partition_value_shadow_supported(prog, fp, cols, T, pt, &vc) || cols.c[vc].validity) return -1;
+  return vc;
+}
+
 const uint32_t* AggregateRelation::Impl::value_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt, int* operand_col) {
   const AggOptions& o = opt();
-  if (o.value_shadow == 0 || calibrating || !(pt.flags & PTF_KEY4) || prog.has_nulls || !input) return nullptr;
-  int vc = 0;
-  if (!partition_value_shadow_supported(prog, fp, cols, T, pt, &vc) || cols.c[vc].validity) return nullptr;
+  const int vc = value_shadow_column(prog, fp, cols, pt);
+  if (vc < 0) return nullptr;
   ScanMemo* memo = input->column_memo();
   if (!memo) return nullptr;
   const ValueShadowDevice dev = shadow_device(ctx().stream, launch_narrow_values, &counters().agg_value_shadow_build_us);
@@ -423,9 +443,28 @@ const uint32_t* AggregateRelation::Impl::value_shadow_words(const DevProgram& pr
   value_shadow_asked = true;
   bool built = false;
   const uint32_t* words = memo->value_shadows.acquire(cols.c[vc].values, o.value_shadow, first, shadow_query_bytes(), dev, &built);
-  if (built) ++counters().agg_value_shadow_builds;
+  if (built) ++counters().agg_value_shadow_builds, shadow_built_here = true;
   *operand_col = vc;
   return words;
+}
+
+// prog, cols: the batch as the operator bound it (before row0).  The layout the launch would be sized by stands in for the
+// launch's flags: the kernels' conditions look at the shape (PTF_WS, PTF_NARROW ...), not at the regions.
+bool AggregateRelation::Impl::both_shadows_bind(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t rows, int64_t row0) {
+  if (opt().routed_row8 == 0 || shadow_built_here || calibrating || !input) return false;
+  const RoutedLayout L = choose_routed_layout(layout_query(rows, prog.has_nulls != 0, true));
+  if (!(L.PT.flags & PTF_ROW8)) return false;  // (not the one-value wave-specialised layout)
+  ScanMemo* memo = input->column_memo();
+  if (!memo) return false;
+  DevPartition pt = L.PT;
+  const int ks = key_shadow_column(prog, fp, cols, pt);
+  if (ks < 0 || !memo->key_shadows.peek(cols.c[ks].values)) return false;
+  DevProgram prog4 = prog;
+  prog4.col_dtype[ks] = T_U32;
+  pt.flags |= PTF_KEY4;
+  const int vc = value_shadow_column(prog4, fp, cols, pt);
+  (void)row0;  // (a slice's shadow words start on the same multiple of 64 rows as its columns: peek looks at the column's base)
+  return vc >= 0 && memo->value_shadows.peek(cols.c[vc].values) != nullptr;
 }
 
 Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgram& prog_in, const DevColumns& cols_in,
@@ -444,14 +483,19 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
   }
   DevAggPlan p = active().plan;
   bool partition_now = dec.use_partition && partition_allowed();
+  const int64_t layout_rows = launch_rows_hint > 0 ? std::max<int64_t>(n, std::min<int64_t>(launch_rows_hint, b.num_rows)) : std::max<int64_t>(n, b.num_rows);  // (the slice after the calibration rows: size for the whole batch)
   if (partition_now) {
-    Status pst = ensure_partition(launch_rows_hint > 0 ? std::max<int64_t>(n, std::min<int64_t>(launch_rows_hint, b.num_rows)) : std::max<int64_t>(n, b.num_rows), prog.has_nulls != 0);  // (the slice after the calibration rows: size for the whole batch)
+    // the row form is the layout's: ask first whether this launch will bind both shadows (8-byte rows), then lay out.  A launch
+    // that will not closes a pending window of 8-byte rows here (the form differs: flush_pass2, regions laid out again)
+    const bool both = both_shadows_bind(prog_in, fast_plan(), cols_in, layout_rows, row0);
+    Status pst = ensure_partition(layout_rows, prog.has_nulls != 0, both);
     if (!pst.ok() && pst.code == DFX_NOT_IMPLEMENTED) partition_now = false;  // global-atomic path instead
     else if (!pst.ok()) return pst;
   }
   if (partition_now) {
     const DevFastPlan fpp = fast_plan();
     DevPartition pt = PT;
+    pt.flags &= ~PTF_ROW8;  // (the shadows first: the form is put back below once both are bound)
     if (win.pending > 0) pt.flags |= PTF_RESUME;
     // the key column's Int32 shadow, bound in place of the column for this launch: 12 bytes per row.  Everything behind the
     // hash image -- routed rows, pass 2, the table, the result's Int64 key column -- is what it was
@@ -473,6 +517,20 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
         bytes -= 4.0 * (double)n;
         ++counters().agg_value_shadow_launches;
         ++value_shadow_launches;
+      }
+    }
+    if (PT.flags & PTF_ROW8) {
+      if (pt.flags & PTF_VAL4) {
+        pt.flags |= PTF_ROW8;
+        ++counters().agg_row8_launches;
+        ++row8_launches;
+      } else {
+        // a shadow that was there a moment ago did not bind after all (memory, a slice off the 64-row grid): 8-byte regions never
+        // meet such a launch -- close the window, lay the regions out for 12-byte rows
+        DFX_RETURN_IF_ERROR(ensure_partition(layout_rows, prog.has_nulls != 0, false));
+        const uint32_t keep = pt.flags & (PTF_KEY4 | PTF_VAL4);
+        pt = PT;
+        pt.flags |= keep;  // (nothing is pending after the flush: no PTF_RESUME)
       }
     }
     // close the window when one more batch could overflow a region (or the batch budget is used up; the calibration

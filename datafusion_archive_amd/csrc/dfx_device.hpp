@@ -321,6 +321,10 @@ enum : uint32_t {
   PTF_VAL4 = 1024u,       // with PTF_KEY4, the two compile-time signatures only: the operand column is bound to its Float32 shadow as
                           // well (every value of the column is exactly that float: checked when the shadow was built).  Key and operand
                           // are loaded as pair words and the operand is widened back (StaticKey4Val4Policy): 8 bytes per row.  Per launch
+  PTF_ROW8 = 2048u,       // with PTF_NARROW | PTF_CHUNK16 | PTF_WS, one aggregate, LINE chunks: every launch of the window binds both shadows
+                          // (PTF_VAL4), so the routed row is 8 bytes {hash image, Float32 bits of the operand} -- sixteen rows are one whole
+                          // 128-byte line (kRow8* below), pass 2 widens the bits (shadow_widen) in front of the atomic.  Part of the LAYOUT
+                          // (choose_routed_layout), unlike PTF_KEY4 / PTF_VAL4: a launch without PTF_VAL4 never meets such regions
   PTF_NARROW = 8u         // keys below 2^32 (seen by the calibration slice): 12-byte routed rows {hash image, operand}, pass 2
                           // works on 32-bit images; needs ring flavour, one key word, one aggregate
 };
@@ -344,6 +348,16 @@ constexpr int kNarrowRingRows = kNarrowChunkRows * kNarrowRingSlots;
 constexpr int kNarrowSlotBytes = kNarrowLine ? 128 : 192;  // LDS bytes (and region bytes) per chunk
 constexpr int kNarrowTripRows = kNarrowLine ? 60 : 64;     // rows of one 768-byte pass-2 trip
 constexpr uint32_t kNarrowCapQuantum = kNarrowLine ? 320u : 64u;  // cap_rows of a PTF_CHUNK16 layout is a multiple of this
+
+// PTF_ROW8: a routed row is two dwords {hash image, Float32 bits}.  Sixteen rows are one 128-byte line with no padding: row r of a
+// region lives at byte r * 8, the ring of a partition is three 128-byte slots as above, pass 2 reads trips of 64 contiguous rows =
+// 512 bytes (one 8-byte load per lane), and 64 rows are both whole lines and whole trips.
+constexpr int kRow8Dwords = 2;
+constexpr int kRow8ChunkRows = 16;
+constexpr int kRow8RingRows = kRow8ChunkRows * kNarrowRingSlots;  // (the form exists under kNarrowLine only: three slots)
+constexpr int kRow8TripRows = 64;
+constexpr uint32_t kRow8TripBytes = 512u;
+constexpr uint32_t kRow8CapQuantum = 64u;  // cap_rows of a PTF_ROW8 layout: whole lines and whole trips
 
 // PTF_PAIR: a routed row is five dwords {operand 0 lo, operand 0 hi, hash image, operand 1 lo, operand 1 hi}: pass 2 of plane 0
 // reads {operand 0, image} at byte 0, pass 2 of plane 1 reads {image, operand 1} at byte 8 -- twelve bytes either way, as of a

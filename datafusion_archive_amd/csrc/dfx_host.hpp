@@ -166,6 +166,7 @@ struct Counters {
   long long agg_key_shadow_build_us = 0;  // ... wall time of the builds (kernel + the read-back of the dropped-halves word)
   long long agg_value_shadow_builds = 0;    // Float32 shadows of resident Float64 operand columns built (once per table and column)
   long long agg_value_shadow_launches = 0;  // pass-1 launches that read the operand from its shadow (PTF_VAL4: 8 bytes per row)
+  long long agg_row8_launches = 0;          // ... that routed 8-byte rows {image, Float32 bits} (PTF_ROW8: every launch of the window bound both shadows)
   long long agg_value_shadow_build_us = 0;  // ... wall time of the build attempts (kernel + the read-back of the not-exact word)
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
   // COUNT(DISTINCT) (dfx_distinct.cpp)

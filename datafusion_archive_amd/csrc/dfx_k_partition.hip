@@ -97,6 +97,8 @@ static Pass1Choice select_pass1(const DevProgram& P, const DevFastPlan& fast, co
   c.lds_bytes = partition_stage_bytes(PT);
   const bool shared = (PT.flags & PTF_SHARED) != 0;
   const bool plan_first = (fast.plan_mode & 3) == 2;  // (A/B: scan.plan = 2)
+  // regions of 8-byte rows (PTF_ROW8) take the launches that bind both shadows and no other: not the caller's word for it
+  if (!partition_row8_consistent(PT.flags)) return c;
   if (PT.flags & PTF_KEY4) {
     // The two signatures that have a two-keys-per-lane kernel (StaticKey4Policy: the wave-specialised kernel alone) describe the
     // 8-byte binding; whatever else the scan plan binds with the key as an unsigned 4-byte column: its one-value kernels
@@ -162,7 +164,7 @@ bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast
   DevProgram P4 = P;
   P4.col_dtype[ks] = T_U32;  // (C's own 8-byte aligned base stands in for the shadow's)
   DevPartition PT4 = PT;
-  PT4.flags |= PTF_KEY4;
+  PT4.flags = (PT4.flags & ~PTF_ROW8) | PTF_KEY4;  // (the question is about the shape; the row form follows from the answers)
   return select_pass1(P4, fast, C, T, PT4).unit != Pass1Unit::none;
 }
 
@@ -177,7 +179,7 @@ bool partition_value_shadow_supported(const DevProgram& P, const DevFastPlan& fa
   DevProgram P4 = P;
   P4.col_dtype[vc] = T_F32;
   DevPartition PT4 = PT;
-  PT4.flags |= PTF_VAL4;
+  PT4.flags = (PT4.flags & ~PTF_ROW8) | PTF_VAL4;
   const Pass1Unit unit = select_pass1(P4, fast, C, T, PT4).unit;
   *operand_col = vc;
   return unit == Pass1Unit::key4_static_key_sum_pred2 || unit == Pass1Unit::key4_static_key_sum;
@@ -201,7 +203,7 @@ hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const 
                             double algo_bytes, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   Scope sc(KID_PARTITION, s, algo_bytes);
-  if (!partition_launchable(PT)) return hipErrorInvalidValue;
+  if (!partition_launchable(PT) || !partition_row8_consistent(PT.flags)) return hipErrorInvalidValue;
   const Pass1Choice c = select_pass1(P, fast, C, T, PT);
   if (c.unit == Pass1Unit::none) return hipErrorNotSupported;
   kPass1Launch[(int)c.unit](P, c.bound ? c.fp : fast, c.bound ? c.cp : C, plan, T, c.PT, spill, n, c.lds_bytes, s);

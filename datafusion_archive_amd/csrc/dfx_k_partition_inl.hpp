@@ -49,9 +49,10 @@ DEV uint32_t* region_row12(const DevPartition& PT, uint32_t part, uint32_t produ
 // is one 128-byte line, in the region and in the LDS ring alike.  Regions of this geometry are contiguous (layouts 0 and 1).
 template <int CH, int NARROW, int DW = 3>
 constexpr bool ring_is_line() {
-  return kNarrowLine && NARROW != 0 && ((DW == 3 && CH == kNarrowChunkRows) || (DW == kPairRowDwords && CH == kPairChunkRows));
+  return kNarrowLine && NARROW != 0 &&
+         ((DW == 3 && CH == kNarrowChunkRows) || (DW == kPairRowDwords && CH == kPairChunkRows) || (DW == kRow8Dwords && CH == kRow8ChunkRows));
 }
-// dword index (from the ring's first dword) of row r of chunk slot sl of partition `part`  (DW: dwords per row -- 3, or 5: PTF_PAIR)
+// dword index (from the ring's first dword) of row r of chunk slot sl of partition `part`  (DW: dwords per row -- 3, 5: PTF_PAIR, or 2: PTF_ROW8, sixteen rows fill the line)
 template <int CH, int RP, int NARROW, int DW = 3>
 DEV uint32_t ring_dword12(uint32_t part, uint32_t sl, uint32_t r) {
   if constexpr (ring_is_line<CH, NARROW, DW>()) return (part * (uint32_t)(RP / CH) + sl) * 32u + r * (uint32_t)DW;
@@ -656,11 +657,13 @@ __device__ __attribute__((noinline)) void ws_slow_rows_call(uint32_t* ctrl, uint
 // KEY_IS_IMG: `key` holds the row's 32-bit hash IMAGE, not its key (the dense split of the wave-specialised kernel: the scanner has
 // hashed the row and turned away what has no image); a row that leaves the routed path gets its key back (unhash_word32)
 // DW = 5 (PTF_PAIR): the row carries a second operand, val2 (20-byte rows, six per 128-byte line: dfx_device.hpp)
+// DW = 2 (PTF_ROW8): `val` holds the operand's Float32 shadow word (8-byte rows, sixteen per line); a row that leaves the routed
+// path is widened here (shadow_widen) and spilled as the Float64 the 12-byte row would have carried
 template <int kRingCH, int kRingRP, int NARROW, bool KEY_IS_IMG = false, int DW = 3>
 DEV void ring_route2(const DevTable& T, const DevPartition& PT, const DevRows& spill, const RingLds& L, uint32_t producer,
                      const bool (&have)[2], const uint64_t (&key)[2], const uint64_t (&val)[2], const uint64_t (&h)[2], uint32_t& err,
                      const uint64_t (&val2)[2]) {
-  static_assert(DW == 3 || (DW == kPairRowDwords && NARROW != 0), "rows of three dwords, or the narrow pair rows");
+  static_assert(DW == 3 || ((DW == kPairRowDwords || DW == kRow8Dwords) && NARROW != 0), "rows of three dwords, the narrow pair rows, or the rows of two shadows");
   constexpr int kRingNCH = kRingRP / kRingCH;
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
@@ -707,7 +710,7 @@ DEV void ring_route2(const DevTable& T, const DevPartition& PT, const DevRows& s
         expand_shared_operand(T, val[b], sv);
       } else {
 #pragma unroll
-        for (int a = 0; a < kMaxAggs; ++a) sv[a] = a == 0 ? val[b] : 0ull;
+        for (int a = 0; a < kMaxAggs; ++a) sv[a] = a == 0 ? (DW == kRow8Dwords ? shadow_widen((uint32_t)val[b]) : val[b]) : 0ull;
       }
       spill_row<1>(T, spill, todo[b], k1, sv);
     }
@@ -742,6 +745,8 @@ DEV void ring_route2(const DevTable& T, const DevPartition& PT, const DevRows& s
             d32[2] = img[b];
             d32[3] = (uint32_t)val2[b];
             d32[4] = (uint32_t)(val2[b] >> 32);
+          } else if constexpr (DW == kRow8Dwords) {
+            *(uint2*)d32 = make_uint2(img[b], (uint32_t)val[b]);
           } else {
             d32[0] = img[b];
             d32[1] = (uint32_t)val[b];

@@ -57,8 +57,13 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
   static_assert(NS >= 1 && NR >= 1 && NR % NS == 0, "every router has a queue, every scanner the same number of them");
   static_assert(NV == 1 || NV == 2, "one routed operand, or the pair");
   // chunk geometry: rows per chunk (= per 128-byte line), rows per ring, dwords per row
-  constexpr int CH = NV == 2 ? kPairChunkRows : kWsCH, RP = NV == 2 ? kPairRingRows : kWsRP, DW = NV == 2 ? kPairRowDwords : 3;
-  static_assert(NV == 1 || !kNarrowLine || RP / CH == kWsNCH, "three slots either way");
+  // R8 (PTF_ROW8, a policy over both shadows): 8-byte rows {image, Float32 bits}, sixteen per line; the queues' operand plane holds
+  // the 4-byte shadow words (the plane's other half stays unused: partition_ws_bytes counts 4 bytes per queue row less)
+  constexpr bool R8 = Row8Of<POL>::value;
+  static_assert(!R8 || (NV == 1 && kNarrowLine), "one routed operand, whole-line chunks");
+  constexpr int CH = NV == 2 ? kPairChunkRows : R8 ? kRow8ChunkRows : kWsCH, RP = NV == 2 ? kPairRingRows : R8 ? kRow8RingRows : kWsRP,
+                DW = NV == 2 ? kPairRowDwords : R8 ? kRow8Dwords : 3;
+  static_assert(!kNarrowLine || RP / CH == kWsNCH, "three slots either way");
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   RingLds L;
   L.ring = lds;
@@ -74,6 +79,7 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
   const size_t qv_word0 = ring_words + ((size_t)(NWAVES * 64 * 2 + PT.n_parts * (1 + 2 * kWsNCH) + NR * kWsQueueRows) * 4 + (size_t)NR * sizeof(WsCtl) + 7) / 8;
   uint64_t* const qvals = lds + qv_word0;                                        // [NR][kWsQueueRows]
   uint64_t* const qvals2 = qvals + (size_t)NR * kWsQueueRows;                    // NV == 2: the second operand, same indexing
+  uint32_t* const qvals32 = (uint32_t*)qvals;                                    // R8: [NR][kWsQueueRows] shadow words
   const int lane = lane_id();
   const int wave = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t producer = blockIdx.x;
@@ -202,7 +208,8 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
               if (lane_of_mask(pm)) {
                 const uint32_t at = (tail + mbcnt64(pm)) & (uint32_t)(kWsQueueRows - 1);
                 qk[at] = qword;
-                qv[at] = val;
+                if constexpr (R8) qvals32[(size_t)(q0 + cq) * kWsQueueRows + at] = POL::pair_raw(col[u & ~1], u & 1);
+                else qv[at] = val;
                 if constexpr (NV == 2) qvals2[(size_t)(q0 + cq) * kWsQueueRows + at] = val1;
               }
               tail += c;
@@ -263,7 +270,8 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
         have[b] = (uint32_t)(b * 64 + lane) < take;
         const uint32_t at = (head + (uint32_t)(b * 64 + lane)) & (uint32_t)(kWsQueueRows - 1);
         k2[b] = have[b] ? (uint64_t)qkeys[(size_t)q * kWsQueueRows + at] : 0ull;
-        v2[b] = have[b] ? qvals[(size_t)q * kWsQueueRows + at] : 0ull;
+        if constexpr (R8) v2[b] = have[b] ? (uint64_t)qvals32[(size_t)q * kWsQueueRows + at] : 0ull;
+        else v2[b] = have[b] ? qvals[(size_t)q * kWsQueueRows + at] : 0ull;
         if constexpr (NV == 2) w2[b] = have[b] ? qvals2[(size_t)q * kWsQueueRows + at] : 0ull;
       }
       // the slots are free again as soon as the rows sit in registers
@@ -351,7 +359,9 @@ void launch_partition_ws(const DevProgram& P, const DevFastPlan& fast, const Dev
 //           eight scanners + eight routers (twelve routers' queues with two operand planes do not fit the LDS), the run-time
 //           comparison form
 //   VAL4    the wave-specialised policy over key AND operand shadows (PTF_VAL4);  VAL4D: of its dense split
-template <typename RING, typename WC, typename NARROW, typename WS = void, typename DENSE = void, typename PAIR = void, typename VAL4 = void, typename VAL4D = void>
+//   ROW8    ... into regions of 8-byte rows (PTF_ROW8);  ROW8D: of its dense split
+template <typename RING, typename WC, typename NARROW, typename WS = void, typename DENSE = void, typename PAIR = void, typename VAL4 = void, typename VAL4D = void,
+          typename ROW8 = void, typename ROW8D = void>
 struct Pass1Policies {
   typedef RING ring;
   typedef WC wc;
@@ -361,6 +371,8 @@ struct Pass1Policies {
   typedef PAIR pair;
   typedef VAL4 val4;
   typedef VAL4D val4_dense;
+  typedef ROW8 row8;
+  typedef ROW8D row8_dense;
 };
 
 // A unit with no other kernels launches its wave-specialised (or pair) kernel whatever the flags say: the host asks for
@@ -371,6 +383,12 @@ void launch_pass1(DFX_PASS1_ARGS) {
   if constexpr (!std::is_void<typename U::pair>::value) {
     if (!has_ws || ((PT.flags & PTF_WS) && (PT.flags & PTF_PAIR))) {
       hipLaunchKernelGGL((k_partition_ws<typename U::pair, (int)kWsDefault, 0, 2>), dim3((int)PT.n_producers), dim3(kRingBlock), lds_bytes, s, P, fast, C, plan, T, PT, spill, n);
+      return;
+    }
+  }
+  if constexpr (!std::is_void<typename U::row8>::value) {  // (select_pass1 has checked the flags: PTF_ROW8 comes with PTF_VAL4 or not at all)
+    if ((PT.flags & PTF_ROW8) && (PT.flags & PTF_VAL4)) {
+      launch_partition_ws<typename U::row8, typename U::row8_dense>(P, fast, C, plan, T, PT, spill, n, lds_bytes, s);
       return;
     }
   }
@@ -393,11 +411,12 @@ void launch_pass1(DFX_PASS1_ARGS) {
 
 // a compile-time signature: four row groups per trip, eight in the dense split;  ... over the key's Int32 shadow (StaticKey4Policy:
 // only the wave-specialised kernel knows it), and over the operand's Float32 shadow as well (StaticKey4Val4Policy, PTF_VAL4: the same
-// two units, the same trips)
+// two units, the same trips; StaticKey4Val4Row8Policy, PTF_ROW8: ... routing the shadow word itself in 8-byte rows)
 template <typename SIG>
 using StaticUnit = Pass1Policies<StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 4, SIG>, StaticPolicy<2, 8, SIG>>;
 template <typename SIG>
-using StaticKey4Unit = Pass1Policies<void, void, void, StaticKey4Policy<4, SIG>, StaticKey4Policy<8, SIG>, void, StaticKey4Val4Policy<4, SIG>, StaticKey4Val4Policy<8, SIG>>;
+using StaticKey4Unit = Pass1Policies<void, void, void, StaticKey4Policy<4, SIG>, StaticKey4Policy<8, SIG>, void, StaticKey4Val4Policy<4, SIG>, StaticKey4Val4Policy<8, SIG>,
+                                     StaticKey4Val4Row8Policy<4, SIG>, StaticKey4Val4Row8Policy<8, SIG>>;
 
 // The scan plan's units (PlanPolicy: range tests on value images, plan words in vector registers): row groups per trip by column
 // class (NC = 2: <= 2 columns; 3: exactly 3 -- key, routed value, one more predicate column, e.g. SUM(w) WHERE v ... GROUP BY k, or
@@ -423,6 +442,8 @@ struct PlanUnit {
   typedef PlanPolicy1<NC, t.dense, GENK> dense;
   typedef void val4;
   typedef void val4_dense;
+  typedef void row8;
+  typedef void row8_dense;
   typedef typename std::conditional<NC >= 3 && !key4, PlanPolicyN<NC, t.ws, GENK>, void>::type pair;  // (+ the PAIR flavour: two aggregates of different operands routed by ONE scan -- PTF_PAIR, dfx_device.hpp)
 };
 // the pair scan over a 4-byte key (GENK = 4: the key in slot 0 is the only 4-byte column -- the Int32 shadow of a resident Int64 key

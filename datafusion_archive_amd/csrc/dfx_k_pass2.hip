@@ -223,6 +223,9 @@ typedef RowForm<12u, true, false, false> RowsNarrow;   // {image, operand}
 typedef RowForm<12u, true, true, false> RowsPair0;     // {operand lo, operand hi, image}
 typedef RowForm<12u, true, false, true> RowsNarrowXf;  // {image, raw operand}
 typedef RowForm<12u, true, true, true> RowsPair0Xf;    // {raw operand lo, hi, image}
+// PTF_ROW8: {image, Float32 bits of the operand} -- 64 contiguous rows per trip, one 8-byte load per lane; the decode widens the bits
+// (shadow_widen: the value the 12-byte row would have carried), so parked rows, the atomic and the spill list see narrow's row
+typedef RowForm<8u, true, false, false> RowsNarrow8;
 
 // The in-flight rows: kPF slots of four registers, outside the register allocator's reach.  The kernel is compiled for
 // kP2Vgprs registers, slot D owns the four that follow: v(kP2Vgprs + 4 D) ... -- v88..v119, which build.py's guard looks for.
@@ -237,8 +240,9 @@ DFX_P2_SLOTS(X)
 static_assert(kPF == 8, "eight row slots in the list");
 struct Row4 { uint32_t x, y, z, w; };
 template <int D, uint32_t ROW_BYTES>
-DEV void p2_issue(uint32_t voff, const void* base) {  // slot D <- the lane's 12 or 16 bytes at base + voff
+DEV void p2_issue(uint32_t voff, const void* base) {  // slot D <- the lane's 8, 12 or 16 bytes at base + voff
 #define X(SLOT, A, B, C, E)                                                                                                                          \
+  if constexpr (D == SLOT && ROW_BYTES == 8u) asm volatile("global_load_dwordx2 v[" #A ":" #B "], %0, %1 nt" ::"v"(voff), "s"(base) : "memory", "v" #A, "v" #B); \
   if constexpr (D == SLOT && ROW_BYTES == 12u) asm volatile("global_load_dwordx3 v[" #A ":" #C "], %0, %1 nt" ::"v"(voff), "s"(base) : "memory", "v" #A, "v" #B, "v" #C); \
   if constexpr (D == SLOT && ROW_BYTES == 16u) asm volatile("global_load_dwordx4 v[" #A ":" #E "], %0, %1 nt" ::"v"(voff), "s"(base) : "memory", "v" #A, "v" #B, "v" #C, "v" #E);
   DFX_P2_SLOTS(X)
@@ -247,7 +251,10 @@ DEV void p2_issue(uint32_t voff, const void* base) {  // slot D <- the lane's 12
 template <int D, uint32_t ROW_BYTES, int N>
 DEV void p2_take(Row4& r) {  // waits until at most N younger loads are in flight, then copies slot D out
   if constexpr (ROW_BYTES == 12u) r.w = 0;
+  if constexpr (ROW_BYTES == 8u) r.z = 0, r.w = 0;
 #define X(SLOT, A, B, C, E)                                                                                                          \
+  if constexpr (D == SLOT && ROW_BYTES == 8u)                                                                                        \
+    asm volatile("s_waitcnt vmcnt(%2)\n\tv_mov_b32 %0, v" #A "\n\tv_mov_b32 %1, v" #B : "=v"(r.x), "=v"(r.y) : "n"(N) : "memory"); \
   if constexpr (D == SLOT && ROW_BYTES == 12u)                                                                                       \
     asm volatile("s_waitcnt vmcnt(%3)\n\tv_mov_b32 %0, v" #A "\n\tv_mov_b32 %1, v" #B "\n\tv_mov_b32 %2, v" #C : "=v"(r.x), "=v"(r.y), "=v"(r.z) : "n"(N) : "memory"); \
   if constexpr (D == SLOT && ROW_BYTES == 16u)                                                                                       \
@@ -377,7 +384,9 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
                                                                                                              const DevRows spill) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   static_assert(!SHARED_OPERAND || ROWS::kTags, "shared-operand rows are narrow rows");
-  static_assert(ROWS::kTags ? ROWS::kRowBytes == 12u : (ROWS::kRowBytes == 16u && !ROWS::kOperandFirst && !ROWS::kPlaneXform), "the five row forms");
+  static_assert(ROWS::kTags ? (ROWS::kRowBytes == 12u || (ROWS::kRowBytes == 8u && !ROWS::kOperandFirst && !ROWS::kPlaneXform && !SHARED_OPERAND))
+                            : (ROWS::kRowBytes == 16u && !ROWS::kOperandFirst && !ROWS::kPlaneXform),
+                "the six row forms");
   const uint32_t NA = SHARED_OPERAND ? (uint32_t)T.na : 1u;
   const uint32_t S = T.block_mask + 1;
   // PTF_PAIR (two aggregates of different operands, 20-byte routed rows): this launch aggregates operand / accumulator plane
@@ -444,7 +453,8 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
   const uint8_t* s_ptr = safe_ptr;
   // LINE chunks (PTF_CHUNK16 with kNarrowLine, dfx_device.hpp): a trip is six 128-byte lines of ten rows -- lane L < 60 reads row
   // L % 10 of line L / 10 --, else 64 contiguous rows; 768 bytes either way
-  const bool line_chunks = ROWS::kTags && kNarrowLine && (PT.flags & PTF_CHUNK16) != 0;
+  // (8-byte rows, PTF_ROW8: sixteen to a line with no padding -- 64 contiguous rows like any other trip)
+  const bool line_chunks = ROWS::kTags && ROWS::kRowBytes == 12u && kNarrowLine && (PT.flags & PTF_CHUNK16) != 0;
   const uint32_t trip_rows = line_chunks ? (uint32_t)kNarrowTripRows : 64u;  // (PTF_PAIR: ten lines of six rows = 60 as well)
   static_assert(kPairTripRows == kNarrowTripRows || !kNarrowLine, "one trip length for both line geometries");
   const uint32_t pair_off = (pair && PT.pair_operand != 0u) ? 8u : 0u;  // operand 1's twelve bytes start at the image
@@ -501,6 +511,12 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
       q.kk = 0;
       q.real = inb && r.z != kTagEmpty;
       q.home4 = (uint32_t)(r.z >> tag_shift) & mask4;
+    } else if (ROWS::kRowBytes == 8u) {  // {image, Float32 bits}: exactly the operand's Float64 bits again
+      q.val = shadow_widen(r.y);
+      q.img = r.x;
+      q.kk = 0;
+      q.real = inb && r.x != kTagEmpty;
+      q.home4 = (uint32_t)(r.x >> tag_shift) & mask4;
     } else if (ROWS::kTags) {
       q.val = ((uint64_t)r.z << 32) | r.y;
       q.img = r.x;
@@ -715,6 +731,10 @@ hipError_t launch_partition_agg(const DevTable& T, const DevPartition& PT, const
         case Pass2Rows::pair0: launch_agg_lean<RowsPair0>(T, Pa, spill, c.lds_bytes, s, a); break;
         case Pass2Rows::narrow_xf: launch_agg_lean<RowsNarrowXf>(T, Pa, spill, c.lds_bytes, s, a); break;
         case Pass2Rows::pair0_xf: launch_agg_lean<RowsPair0Xf>(T, Pa, spill, c.lds_bytes, s, a); break;
+        case Pass2Rows::narrow8:  // (only the two SUM signatures bind both shadows: one accumulator kind)
+          if (T.acc_kind[a] != ACC_ADD_F64) return hipErrorInvalidValue;
+          hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow8, ACC_ADD_F64>), grid, block, c.lds_bytes, s, T, Pa, spill);
+          break;
       }
     }
   }

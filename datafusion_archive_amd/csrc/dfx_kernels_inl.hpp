@@ -874,6 +874,19 @@ struct StaticKey4Val4Policy : StaticPolicy<2, U_, SIG> {
     return row;
   }
 };
+// ... for regions of 8-byte rows (PTF_ROW8: every launch of the window binds both shadows).  The same loads, the same predicate
+// over the widened operand; what the scanner hands the router is the operand's shadow word itself (pair_raw) -- the aggregate is
+// SUM of the plain operand column, so the widened word is the routed value and pass 2 does that widening (shadow_widen).
+template <int U_, typename SIG>
+struct StaticKey4Val4Row8Policy : StaticKey4Val4Policy<U_, SIG> {
+  typedef typename StaticKey4Val4Policy<U_, SIG>::COLV COLV;
+  static constexpr bool kRow8 = true;
+  static constexpr int KC = SIG::key_col(0);
+  static_assert(SIG::NA == 1 && !SIG::arg_dyn(0) && SIG::arg_col(0) == 1 - KC && SIG::xf(0) == VT_RAW, "the routed value is the operand column itself");
+  static DEV uint32_t pair_raw(const COLV& pairs, int b) { return b ? (uint32_t)(pairs[1 - KC] >> 32) : (uint32_t)pairs[1 - KC]; }
+};
+template <typename POL, typename = void> struct Row8Of { static constexpr bool value = false; };
+template <typename POL> struct Row8Of<POL, std::enable_if_t<POL::kRow8>> { static constexpr bool value = true; };
 template <typename POL, typename = void> struct RowPairsOf { static constexpr bool value = false; };
 template <typename POL> struct RowPairsOf<POL, std::enable_if_t<POL::kRowPairs>> { static constexpr bool value = true; };
 template <typename POL, typename = void> struct KeyPairsOf { static constexpr bool value = false; };

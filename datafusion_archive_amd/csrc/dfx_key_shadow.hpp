@@ -85,6 +85,19 @@ class KeyShadows {
     if (!k->narrow) return nullptr;
     return (const uint32_t*)k->narrow.get() + off / 8;
   }
+  // ... as they stand: the words if the copy exists, null otherwise.  Counts nothing, builds nothing.
+  const uint32_t* peek(const void* values) const {
+    if (!values) return nullptr;
+    std::lock_guard<std::mutex> lk(mu_);
+    for (const KeyShadow& c : cols_) {
+      const uint8_t* b = (const uint8_t*)c.base;
+      if ((const uint8_t*)values < b || (const uint8_t*)values >= b + (size_t)c.rows * 8) continue;
+      const size_t off = (size_t)((const uint8_t*)values - b);
+      if (c.refused || !c.narrow || (off & 511u)) return nullptr;
+      return (const uint32_t*)c.narrow.get() + off / 8;
+    }
+    return nullptr;
+  }
   size_t bytes_held() const {
     std::lock_guard<std::mutex> lk(mu_);
     size_t b = 0;

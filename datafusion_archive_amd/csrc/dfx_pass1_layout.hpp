@@ -20,7 +20,7 @@ constexpr int kRingBlock = 1024;
 constexpr int kHotSlots = 1024;        // hot-key pairs per pass-1 workgroup, 16-byte rows
 constexpr int kHotSlotsNarrow = 2048;  // ... with 12-byte rows (the ring is 16 KB smaller)
 constexpr int kSortMaxCap = 8192;  // LDS buffer rows (upper bound: 13-bit row index in the permutation word)
-constexpr int kWsQueueRows = 256;  // per scanner wave (power of two): 3 KB {u32 key, u64 operand}
+constexpr int kWsQueueRows = 256;  // per scanner wave (power of two): 3 KB {u32 key, u64 operand}; PTF_ROW8: 2 KB {u32 key, u32 Float32 bits}
 constexpr int kWsCH = kNarrowChunkRows, kWsRP = kNarrowRingRows, kWsNCH = kWsRP / kWsCH;  // (dfx_device.hpp: LINE chunks of ten rows, three slots)
 
 struct WsCtl {  // one per queue (= per router wave)
@@ -41,10 +41,11 @@ inline size_t partition_ring_bytes(uint32_t n_words, uint32_t n_parts, int kRing
 }
 
 // LDS of the wave-specialised pass-1 kernel (PTF_WS)
-inline size_t partition_ws_bytes(uint32_t n_parts, int ns, int nv = 1) {  // nv: routed operands per row (2: PTF_PAIR -- a second operand plane per queue)
+// row8 (PTF_ROW8): the queues' operand plane holds 4-byte words; the ring is three 128-byte slots per partition either way
+inline size_t partition_ws_bytes(uint32_t n_parts, int ns, int nv = 1, bool row8 = false) {  // nv: routed operands per row (2: PTF_PAIR -- a second operand plane per queue)
   const int nq = kRingBlock / 64 - ns;  // one queue per ROUTER wave (a scanner feeds (16 - ns) / ns of them in turn)
   return (size_t)n_parts * kNarrowRingSlots * kNarrowSlotBytes + (size_t)(kRingBlock / 64) * 64 * 8 /* jobs */ + (size_t)n_parts * 4 * (1 + 2 * kWsNCH) +
-         (size_t)nq * kWsQueueRows * (4 + 8 * (size_t)nv) + (size_t)nq * sizeof(WsCtl) + 64;
+         (size_t)nq * kWsQueueRows * (4 + (row8 ? 4 : 8 * (size_t)nv)) + (size_t)nq * sizeof(WsCtl) + 64;
 }
 
 // LDS rows of the write-combining buffer for a workgroup of `block` lanes and an LDS budget
@@ -60,7 +61,7 @@ inline uint32_t partition_sort_capacity(uint32_t n_words, uint32_t n_parts, uint
 // dynamic LDS of the pass-1 launch of this layout
 inline size_t partition_stage_bytes(const DevPartition& PT) {
   if ((PT.mode & 15u) == 0) return (size_t)PT.n_parts * 4 + 16;
-  if ((PT.mode & 15u) == 2 && (PT.flags & PTF_WS)) return partition_ws_bytes(PT.n_parts, PT.ws_scanners == 4 ? 4 : 8, (PT.flags & PTF_PAIR) ? 2 : 1);
+  if ((PT.mode & 15u) == 2 && (PT.flags & PTF_WS)) return partition_ws_bytes(PT.n_parts, PT.ws_scanners == 4 ? 4 : 8, (PT.flags & PTF_PAIR) ? 2 : 1, (PT.flags & PTF_ROW8) != 0);
   if ((PT.mode & 15u) == 2)
     return partition_ring_bytes(PT.n_words, PT.n_parts, (PT.flags & PTF_CHUNK16) ? kNarrowRingRows : (PT.mode & 0x100u) ? 8 : 16, (PT.flags & PTF_HOT) != 0,
                                 (PT.flags & PTF_NARROW) != 0, (PT.flags & PTF_SHARED) ? 128 : 0);
@@ -84,11 +85,19 @@ inline bool partition_launchable(const DevPartition& PT) {
   return true;
 }
 
+// PTF_ROW8 regions hold 8-byte rows of Float32 bits: only a wave-specialised one-value launch that binds both shadows (PTF_VAL4)
+// writes them.  select_pass1 / launch_partition refuse every other combination (hipErrorInvalidValue).
+inline bool partition_row8_consistent(uint32_t flags) {
+  if (!(flags & PTF_ROW8)) return true;
+  const uint32_t need = PTF_NARROW | PTF_CHUNK16 | PTF_WS | PTF_KEY4 | PTF_VAL4;
+  return kNarrowLine && (flags & need) == need && !(flags & (PTF_SHARED | PTF_PAIR | PTF_PLANES | PTF_HOT));
+}
+
 // ---- the routed layouts ---------------------------------------------------------------------------------------------------------
 // shared_ring: 16-row rings of {image, raw operand} rows, 2..3 aggregates of one operand (PTF_SHARED); planes: the same rows through
 // the wave-specialised kernel, one pass 2 per accumulator plane (PTF_PLANES); pair_rows: 20-byte rows of two operands (PTF_PAIR);
 // ring16: the 16-row ring family -- hot-key pairs (PTF_HOT), large chunks (PTF_CHUNK16) and wave specialisation (PTF_WS) are
-// properties of it; ring8: 8-row rings for rows of three and more words; sort: the LDS counting sort; direct: a store per row.
+// properties of it, and so is the 8-byte row of two shadows (PTF_ROW8); ring8: 8-row rings for rows of three and more words; sort: the LDS counting sort; direct: a store per row.
 enum class RoutedLayoutKind : int { refused_pair_scan = -2, refused_table_blocks = -1, shared_ring, planes, pair_rows, ring16, ring8, sort, direct };
 constexpr const char* kRoutedLayoutName[] = {"shared_ring", "planes", "pair_rows", "ring16", "ring8", "sort", "direct"};
 
@@ -115,12 +124,15 @@ struct RoutedLayoutQuery {
   bool has_pred, unfused_now;
   bool narrow, dense_seen, mostly_seen, skew_seen;  // StrategyDecision
   Pass1LayoutOptions opt;
+  // every launch sized by this layout will bind both column shadows (PTF_VAL4): the one-value wave-specialised layout then routes
+  // 8-byte rows (PTF_ROW8).  false: the layout as it is without the form
+  bool both_shadows = false;
 };
 
 struct RoutedLayout {
   RoutedLayoutKind kind = RoutedLayoutKind::refused_pair_scan;
   DevPartition PT = {};  // every field that is not a pointer (refused_table_blocks: n_parts, n_words and part_shift alone)
-  // PTF_NARROW | PTF_SHARED | PTF_PAIR | PTF_PLANES as the query WANTS them: what ensure_partition compares the layout in use with
+  // PTF_NARROW | PTF_SHARED | PTF_PAIR | PTF_PLANES as the query WANTS them (and PTF_ROW8 as the layout HAS it): what ensure_partition compares the layout in use with
   // ("same table, keep appending").  An oddity, kept: PTF_NARROW is wanted for every narrow one-value query, but only the ring
   // family's 12-byte rows set it -- under ring8, sort, direct and agg.partition_mode = 2 | 0x80 such a query never finds its own
   // layout "the same" and lays the regions out again (a pass 2) with every batch.
@@ -214,6 +226,11 @@ inline RoutedLayout choose_routed_layout(const RoutedLayoutQuery& q) {
       PT.ws_scanners = ws_scanners;  // (an oddity, kept: it stays set when the kernel's LDS does not fit and PTF_WS is not)
       if (partition_ws_bytes(PT.n_parts, (int)PT.ws_scanners) <= kPass1LdsBudget) PT.flags |= PTF_WS;
     }
+    // both shadows bound by every launch: {image, Float32 bits}, sixteen rows per line (the operand's 4 shadow bytes ARE the operand)
+    if (q.both_shadows && kNarrowLine && (PT.flags & PTF_WS) && q.na == 1 && q.kw == 1) {
+      PT.flags |= PTF_ROW8;
+      r.want_flags |= PTF_ROW8;
+    }
     PT.mode = 2u | mode_bits;
   } else if (want == 2 && partition_ring_bytes(PT.n_words, PT.n_parts, 8) <= kPass1LdsBudget) {
     // several aggregates: rows of 3+ words.  8-row rings (two 4-row chunks) still fit where 16-row ones do not
@@ -236,7 +253,8 @@ inline RoutedLayout choose_routed_layout(const RoutedLayoutQuery& q) {
   // capacities are whole 64-row trips; LINE chunks (ten rows per 128-byte line, PTF_CHUNK16): whole lines as well
   const bool pair_rows = (PT.flags & PTF_PAIR) != 0;                  // a region is cap_rows / 6 lines of 128 bytes
   const bool line_chunks = (PT.flags & PTF_CHUNK16) && kNarrowLine;  // ... cap_rows / 10 lines
-  const uint64_t capq = pair_rows ? (uint64_t)kPairCapQuantum : line_chunks ? (uint64_t)kNarrowCapQuantum : 64ull;
+  const bool row8 = (PT.flags & PTF_ROW8) != 0;                       // ... cap_rows / 16 lines, no padding: cap_rows * 8 bytes
+  const uint64_t capq = pair_rows ? (uint64_t)kPairCapQuantum : row8 ? (uint64_t)kRow8CapQuantum : line_chunks ? (uint64_t)kNarrowCapQuantum : 64ull;
   r.worst = (uint32_t)((2 * avg + 64 + capq - 1) / capq * capq);
   // regions hold `window` worst-case batches.  Deferral pays when few rows are routed (headline, 20 %: 2 batches per
   // pass 2 = -3 % per query); when most rows are, the twice-as-long regions cost pass 1 more than the saved launches
@@ -252,10 +270,11 @@ inline RoutedLayout choose_routed_layout(const RoutedLayoutQuery& q) {
   uint64_t pad_words = (uint64_t)(o.partition_pad >= 0 ? o.partition_pad : 0) / 8;
   if (line_chunks) pad_words = (pad_words + 15) / 16 * 16;  // (every region starts on a 128-byte line)
   const uint64_t region_words = pair_rows ? (uint64_t)(PT.cap_rows / (uint32_t)kPairChunkRows) * 16u
+                                : row8 ? (uint64_t)PT.cap_rows * (4u * kRow8Dwords) / 8
                                 : line_chunks ? (uint64_t)(PT.cap_rows / (uint32_t)kNarrowChunkRows) * (kNarrowSlotBytes / 8)
                                 : (PT.flags & PTF_NARROW) ? (uint64_t)PT.cap_rows * 12 / 8 : (uint64_t)PT.cap_rows * PT.n_words;
   // one pass-2 trip's worth (64 contiguous rows, or six LINE chunks = 60 rows: 768 bytes either way): regions are contiguous (layouts 0 and 1)
-  PT.win_stride = pair_rows ? (uint64_t)(kPairTripBytes / 8u) : line_chunks ? 96u : region_words / (PT.cap_rows / 64);
+  PT.win_stride = pair_rows ? (uint64_t)(kPairTripBytes / 8u) : row8 ? (uint64_t)(kRow8TripBytes / 8u) : line_chunks ? 96u : region_words / (PT.cap_rows / 64);
   uint64_t row_words;
   if (o.partition_layout == 2) {  // windowed: window w of every partition of a producer side by side
     PT.part_stride = PT.win_stride;

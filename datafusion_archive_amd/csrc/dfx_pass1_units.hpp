@@ -14,7 +14,8 @@ namespace dfx {
 // the GENK the kernels are compiled for: bit 0 4-byte columns widened, bit 1 validity bitmaps, bit 2 (instead of bit 0) the
 // key is the only 4-byte column (the multi-value flavours of the g4 / g6 units are never launched: bit 2 belongs to the one-key,
 // one-value binding).  key4_*: the signature over the key column's Int32 shadow, two keys per lane (PTF_KEY4; the
-// wave-specialised kernel alone).  pair_key4_*: the pair scan over a 4-byte key, 3 / 4 columns (the pair kernel alone; the pair
+// wave-specialised kernel alone; the same two units hold the kernels over both shadows, PTF_VAL4, and those that route 8-byte
+// rows, PTF_ROW8).  pair_key4_*: the pair scan over a 4-byte key, 3 / 4 columns (the pair kernel alone; the pair
 // scan over 8-byte keys is a flavour of plan_c3_* / plan_c4_* g0..g3).
 #define DFX_PASS1_UNITS(X)                                                                   \
   X(static_key_sum_pred2) X(static_key_sum) X(static_key_aff_sum_pred2)                      \

@@ -14,14 +14,16 @@ namespace dfx {
 // flat_*: k_partition_agg, the producers' rows as one flattened index space (one 16-byte value / any row width).  The others are
 // k_partition_agg_lean, a wave per region: stream_wide 16-byte rows and keys in LDS; narrow 12-byte rows and tags; shared_operand
 // narrow rows, 2..kSharedMaxAggs accumulators of the one raw operand in ONE launch; planes the same rows, one launch per
-// accumulator plane; pair 20-byte rows of two operands, one launch per plane; pair_planes both.
+// accumulator plane; pair 20-byte rows of two operands, one launch per plane; pair_planes both.  (The 8-byte rows of PTF_ROW8 are
+// the narrow FORM -- same block, same LDS, one launch -- with a row of their own: Pass2Rows::narrow8.)
 enum class Pass2Form : int { refused = -1, flat_one, flat_any, stream_wide, narrow, shared_operand, planes, pair, pair_planes };
 constexpr const char* kPass2FormName[] = {"flat_one", "flat_any", "stream_wide", "narrow", "shared_operand", "planes", "pair", "pair_planes"};
 
-// The twelve or sixteen bytes of a routed row that a lane of k_partition_agg_lean loads (the Rows* policies of dfx_k_pass2.hip):
+// The eight, twelve or sixteen bytes of a routed row that a lane of k_partition_agg_lean loads (the Rows* policies of dfx_k_pass2.hip):
 // wide {key, operand}, the block holds keys; narrow {image, operand}, the block holds 32-bit tags; pair0 {operand lo, operand hi,
-// image}: operand 0 of a 20-byte pair row; *_xf: the operand is raw, the launch applies its plane's transform.
-enum class Pass2Rows : int { wide, narrow, pair0, narrow_xf, pair0_xf };
+// image}: operand 0 of a 20-byte pair row; *_xf: the operand is raw, the launch applies its plane's transform; narrow8 {image,
+// Float32 bits}: the decode widens the bits (shadow_widen), everything behind it is narrow's.
+enum class Pass2Rows : int { wide, narrow, pair0, narrow_xf, pair0_xf, narrow8 };
 
 constexpr int kP2Waves = 16;          // waves of a pass-2 workgroup (kABlock / 64)
 constexpr int kP2RetryRows = 128;     // per-wave queue of rows that missed their home group (narrow rows: 12 bytes each)
@@ -47,7 +49,8 @@ constexpr bool pass2_is_pair(Pass2Form f) { return f == Pass2Form::pair || f == 
 constexpr bool pass2_per_plane(Pass2Form f) { return f == Pass2Form::planes || pass2_is_pair(f); }
 
 // Dynamic LDS of a launch.  flat_*: the block's key and accumulator planes, the prefix of the producer counts.  The others: the
-// block -- keys or 4-byte tags, and the accumulator planes of ONE launch -- and sixteen per-wave queues of parked rows.
+// block -- keys or 4-byte tags, and the accumulator planes of ONE launch -- and sixteen per-wave queues of parked rows (narrow8 rows:
+// a parked row is widened first and stays twelve bytes, so its bytes are narrow's).
 constexpr size_t pass2_lds_bytes(Pass2Form f, uint32_t slots, int na, uint32_t n_producers) {
   if (f == Pass2Form::flat_one || f == Pass2Form::flat_any) return (size_t)slots * (size_t)(1 + na) * 8 + (size_t)(n_producers + 1) * 4 + 16;
   if (f == Pass2Form::stream_wide) return (size_t)slots * 16 + (size_t)kP2Waves * kP2RetryRowsWide * 16;
@@ -94,6 +97,10 @@ inline Pass2Choice choose_pass2(uint32_t flags, int na, int kw, uint32_t n_words
         if (((pair_ops >> b) & 1u) == l.operand) l.plane_spills = 0u;
       l.keeps_snap = a + 1 == na;
     }
+  } else if (flags & PTF_ROW8) {
+    if (na != 1 || kw != 1 || !narrow_line || !(flags & PTF_CHUNK16)) return refused;
+    take(Pass2Form::narrow, 1);
+    c.launch[0].rows = Pass2Rows::narrow8;
   } else {
     if (na != 1 || kw != 1) return refused;
     take(Pass2Form::narrow, 1);

@@ -85,6 +85,9 @@ struct AggOptions {
   int value_shadow = -1;       // the Float32 shadow of a resident table's null-free Float64 operand column whose every value is Float32-exact
                                // (dfx_value_shadow.hpp: with the key shadow pass 1 reads 8 bytes per row instead of 12; no bit of any result
                                // changes): -1 / 0 / 1 as agg.key_shadow
+  int routed_row8 = -1;        // 8-byte routed rows {hash image, Float32 bits} in the one-value wave-specialised layout when every launch of a
+                               // window binds both shadows (PTF_ROW8: pass 1 appends 8 bytes per routed row instead of 12.8, pass 2 widens):
+                               // -1 by that rule, 0 never
   int partition_layout = 1;    // routing scratch: 1 producer-major, 0 partition-major (round 1), 2 windowed (DevPartition::win_stride;
                                // measured no better for the filtered query and 17 % worse in pass 1 when every row is routed)
   int partition_producers = 0; // pass-1 workgroups of the ring flavour (0: one per CU)

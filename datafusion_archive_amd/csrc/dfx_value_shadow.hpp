@@ -27,6 +27,7 @@ class ValueShadows {
   const uint32_t* acquire(const void* values, int option, bool first_ask, size_t query_bytes, const ValueShadowDevice& dev, bool* built) {
     return rule_.acquire(values, option, first_ask, query_bytes, dev, built);
   }
+  const uint32_t* peek(const void* values) const { return rule_.peek(values); }  // the words if the copy exists; no side effects
   size_t bytes_held() const { return rule_.bytes_held(); }
   // (tests) -1 unknown, 0 nothing built, 1 built, 2 refused (not Float32-exact); *queries: askers so far
   int state_of(const void* values, int* queries = nullptr) const { return rule_.state_of(values, queries); }
