@@ -10,6 +10,7 @@
 //   A FilterRelation feeding the aggregate (context.rs:126-139,162-192) is absorbed: its predicate
 //   becomes part of the fused program and no filtered batch is ever materialised.
 #include "dfx_aggregate_impl.hpp"
+#include "dfx_row_source.hpp"
 
 namespace dfx {
 
@@ -494,22 +495,14 @@ void AggregateRelation::explain(std::string* out, int depth) const {
     explain_line(out, depth, "Aggregate: error deferred to next(): " + m.deferred.msg);
   } else {
     const DevProgram& P = m.active().builder->program();
-    const char* shape = "SSA interpreter";
-    if (m.kw == 0) {
-      if (sig_matches<SigCountPred2F64>(P, m.active().fast, 0, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape CountPred2F64";
-      else if (sig_matches<SigSumCountPred2F64>(P, m.active().fast, 0, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape SumCountPred2F64";
-      else if (m.opt().plan != 0 && scan_plan_shape_ok(P, m.active().fast, 0, m.na(), m.val_xform())) shape = "scan plan where a batch has nulls or 4-byte columns (PlanPolicy: range tests on value images), else column-op-literal shape (FastPolicy)";
-      else if (m.active().fast.valid) shape = "column-op-literal shape (FastPolicy; interpreter when a batch has nulls)";
-    } else {
-      if (m.kw == 1 && sig_matches<SigKeySumPred2F64>(P, m.active().fast, 1, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape KeySumPred2F64";
-      else if (m.kw == 1 && sig_matches<SigKeyAffSumPred2F64>(P, m.active().fast, 1, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape KeyAffSumPred2F64 (pass 1 of the partitioned strategy)";
-      else if (m.kw == 1 && sig_matches<SigKeySum>(P, m.active().fast, 1, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape KeySum";
-      else if (m.kw == 2 && sig_matches<SigQ1>(P, m.active().fast, 2, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape Q1";
-      else if (m.opt().plan != 0 && scan_plan_shape_ok(P, m.active().fast, m.kw, m.na(), m.val_xform()))
-        shape = m.kw == 1 ? "scan plan (PlanPolicy: range tests on value images, 4-byte columns widened, nulls by arrow's rule; every kernel of the partitioned strategy, the other strategies where a batch has nulls or 4-byte columns)"
-                          : "scan plan where a batch has nulls or 4-byte columns (PlanPolicy), else column-op-literal shape (FastPolicy)";
-      else if (m.active().fast.valid) shape = "column-op-literal shape (FastPolicy; interpreter when a batch has nulls)";
-    }
+    // the row source in words: the launchers' own choice (dfx_row_source.hpp) for the program as built -- no batch is bound, so the
+    // scan plan wherever one can be built
+    DevFastPlan F = m.active().fast;
+    F.plan_mode = m.opt().plan;
+    const ScanKernel kernel = m.kw == 0 ? ScanKernel::reduce : ScanKernel::hash_agg;
+    const char* shape = row_source_prose(kernel, row_source_without_batch(kernel, P, F, m.kw, m.na(), m.acc_kind(), m.val_xform(),
+                                                                           scan_plan_shape_ok(P, F, m.kw, m.na(), m.val_xform())), m.kw);
+    if (m.kw == 1 && sig_matches<SigKeyAffSumPred2F64>(P, F, 1, m.na(), m.acc_kind(), m.val_xform())) shape = "static shape KeyAffSumPred2F64 (pass 1 of the partitioned strategy)";
     std::string text = strfmt("Aggregate: %d keys%s, %d accumulators", m.kw_out, m.kw != m.kw_out ? " (as 8 key words)" : "", m.na_total);
     if (m.chunks.size() > 1) text += strfmt(" in %d chunks of <= %d (one fused program each, the same table)", (int)m.chunks.size(), kMaxAggs);
     const bool plan_fuses = m.opt().plan != 0 && m.opt().fast != 0 && scan_plan_shape_ok(P, m.active().fast, m.kw, m.na(), m.val_xform());

@@ -2,7 +2,7 @@
 // three ways to a bitmap (a Utf8 term's own, the single-pass kernel, mask -> AND -> scan) and the per-column compaction;
 // its C-ABI constructors and the test hook that reads the bitmap back.
 #include "dfx_relation.hpp"
-#include "dfx_sigs.hpp"
+#include "dfx_row_source.hpp"
 
 #include <string.h>
 
@@ -104,9 +104,7 @@ void FilterRelation::explain(std::string* out, int depth) const {
   } else {
     const uint8_t none[kMaxAggs] = {0};
     const DevProgram& P = builder_->program();
-    const char* shape = sig_matches<SigPred2F64>(P, fast_, 0, 0, none, none) ? "static shape Pred2F64"
-                        : fast_.valid                                       ? "column-op-literal conjunction (FastPolicy; interpreter when a batch has nulls)"
-                                                                            : "SSA interpreter";
+    const char* shape = row_source_prose(ScanKernel::filter_fused, row_source_without_batch(ScanKernel::filter_fused, P, fast_, 0, 0, none, none, false), 0);
     int n = 0;
     for (size_t i = 0; i < schema_.fields.size() || i < out_needed_.size(); ++i) n += (out_needed_.empty() || (i < out_needed_.size() && out_needed_[i])) ? 1 : 0;
     const bool single = more_.empty() && opt_.get().filter_single_pass;

@@ -172,22 +172,21 @@ template <int KW>
 hipError_t distinct_insert(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan, int kw_out,
                            const DevTable& T, const DevRows& spill, int64_t n, bool* plan_kernel, hipStream_t s) {
   const int grid = stream_grid((n + kBlock - 1) / kBlock, 8);
-  *plan_kernel = false;
   // plain columns (nulls and 4-byte columns included): the scan plan's loads; anything else: the SSA interpreter
-  DevFastPlan fp;
-  DevColumns cp;
   const uint8_t xf[kMaxAggs] = {VT_RAW, VT_RAW, VT_RAW, VT_RAW, VT_RAW, VT_RAW, VT_RAW, VT_RAW};
-  if ((fast.plan_mode & 3) != 0 && fast.valid && bind_scan_plan(P, fast, C, kw_out, 1, xf, false, &fp, &cp)) {
-    *plan_kernel = true;
-    if (fp.scan.n_cols <= 2)
-      hipLaunchKernelGGL((k_distinct_insert<KW, PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>), dim3(grid), dim3(kBlock), 0, s, P, fp, cp, plan, kw_out, T, spill, n);
-    else
-      hipLaunchKernelGGL((k_distinct_insert<KW, PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>), dim3(grid), dim3(kBlock), 0, s, P, fp, cp, plan, kw_out, T, spill, n);
+  const BoundRowSource b = bind_row_source(ScanKernel::distinct_insert, P, fast, C, kw_out, 1, xf, xf);
+  *plan_kernel = is_plan(b.source);
+  auto run = [&](auto pol) {
+    hipLaunchKernelGGL((k_distinct_insert<KW, typename decltype(pol)::type>), dim3(grid), dim3(kBlock), 0, s, P, b.F(fast), b.C(C), plan, kw_out, T, spill, n);
     return hipGetLastError();
+  };
+  switch (b.source) {
+    case RowSource::plan_c2: return run(Policy<PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>{});
+    case RowSource::plan_c4: return run(Policy<PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>{});
+    case RowSource::interp_c4: return run(Policy<InterpPolicy<4, 4>>{});
+    case RowSource::interp_c8: return run(Policy<InterpPolicy<8, 2>>{});
+    default: return hipErrorNotSupported;  // (no other source in this kernel's ladder)
   }
-  if (P.n_cols <= 4) hipLaunchKernelGGL((k_distinct_insert<KW, InterpPolicy<4, 4>>), dim3(grid), dim3(kBlock), 0, s, P, fast, C, plan, kw_out, T, spill, n);
-  else hipLaunchKernelGGL((k_distinct_insert<KW, InterpPolicy<8, 2>>), dim3(grid), dim3(kBlock), 0, s, P, fast, C, plan, kw_out, T, spill, n);
-  return hipGetLastError();
 }
 
 template <int KW>

@@ -16,6 +16,7 @@
 // Replaces (for this case) the per-row work of with_group_by + update_accumulators
 // (aggregate.rs:787-875, :548-612).  Chosen by the host after the calibration slice reported <= 8 groups.
 #include <algorithm>
+#include <type_traits>
 
 #include "dfx_kernels_inl.hpp"
 #include "dfx_launch.hpp"
@@ -303,11 +304,10 @@ __global__ __launch_bounds__(kFGBlock) void k_fewgroup_agg(const DevProgram P, c
 
 static_assert(kFGSlots == 64, "the flush uses one wave");
 
-// host: can the few-group kernel run this scan?
+// host: can the few-group kernel run this scan?  (launch_fewgroup_agg's own choice, the plan taken as bound where one can be built)
 bool fewgroup_supported(const DevProgram& P, const DevFastPlan& fast, const DevTable& T) {
-  if (!(T.kw >= 1 && T.kw <= 2 && T.na >= 1 && T.na <= 4)) return false;
-  if (fast.valid && !P.has_nulls) return true;
-  return (fast.plan_mode & 3) != 0 && scan_plan_shape_ok(P, fast, T.kw, T.na, T.val_xform);  // (validity bitmaps: a scan plan)
+  return row_source_without_batch(ScanKernel::fewgroup, P, fast, T.kw, T.na, T.acc_kind, T.val_xform,
+                                  scan_plan_shape_ok(P, fast, T.kw, T.na, T.val_xform)) != RowSource::none;
 }
 
 hipError_t launch_fewgroup_agg(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,
@@ -317,39 +317,21 @@ hipError_t launch_fewgroup_agg(const DevProgram& P, const DevFastPlan& fast, con
   Scope sc(KID_HASH_AGG, s, algo_bytes);
   const int64_t n_blocks = (n + kFGBlock - 1) / kFGBlock;
   const int grid = (int)std::min<int64_t>(n_blocks, device_cu_count());
-#define DFX_FG(KW, POL) hipLaunchKernelGGL((k_fewgroup_agg<KW, 4, POL>), dim3(grid), dim3(kFGBlock), 0, s, P, fast, C, plan, T, spill, n)
-  if (T.kw == 2 && sig_matches<SigQ1>(P, fast, T.kw, T.na, T.acc_kind, T.val_xform)) {
-    DFX_FG(2, DFX_ARG(StaticPolicy<8, 2, SigQ1>));
+  const BoundRowSource b = bind_row_source(ScanKernel::fewgroup, P, fast, C, T.kw, T.na, T.acc_kind, T.val_xform);
+  auto run = [&](auto kw, auto pol) {
+    hipLaunchKernelGGL((k_fewgroup_agg<decltype(kw)::value, 4, typename decltype(pol)::type>), dim3(grid), dim3(kFGBlock), 0, s, P, b.F(fast), b.C(C), plan, T, spill, n);
     return hipGetLastError();
+  };
+  auto run_kw = [&](auto pol) { return T.kw == 1 ? run(std::integral_constant<int, 1>{}, pol) : run(std::integral_constant<int, 2>{}, pol); };
+  switch (b.source) {
+    case RowSource::sig_q1: return run(std::integral_constant<int, 2>{}, Policy<StaticPolicy<8, 2, SigQ1>>{});
+    case RowSource::plan_c2: return run_kw(Policy<PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>{});
+    case RowSource::plan_c4: return run_kw(Policy<PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>{});
+    case RowSource::fast_c2: return run_kw(Policy<FastPolicy<2, 4>>{});
+    case RowSource::fast_c4: return run_kw(Policy<FastPolicy<4, 4>>{});
+    case RowSource::fast_c8: return run_kw(Policy<FastPolicy<8, 2>>{});
+    default: return hipErrorNotSupported;  // (the plan this batch needs did not bind: fewgroup_supported took it as bound)
   }
-  if (P.has_nulls || !P.wide8 || (fast.plan_mode & 3) == 2) {  // validity bitmaps / 4-byte columns: the scan plan (see table_hash_agg)
-    DevFastPlan fp;
-    DevColumns cp;
-    if (bind_scan_plan(P, fast, C, T.kw, T.na, T.val_xform, false, &fp, &cp)) {
-#define DFX_FGP(KW, POL) hipLaunchKernelGGL((k_fewgroup_agg<KW, 4, POL>), dim3(grid), dim3(kFGBlock), 0, s, P, fp, cp, plan, T, spill, n)
-      if (T.kw == 1) {
-        if (fp.scan.n_cols <= 2) DFX_FGP(1, DFX_ARG(PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>));
-        else DFX_FGP(1, DFX_ARG(PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>));
-      } else {
-        if (fp.scan.n_cols <= 2) DFX_FGP(2, DFX_ARG(PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>));
-        else DFX_FGP(2, DFX_ARG(PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>));
-      }
-#undef DFX_FGP
-      return hipGetLastError();
-    }
-    if (P.has_nulls || (fast.plan_mode & 4)) return hipErrorNotSupported;  // (fewgroup_supported said yes for a plan only)
-  }
-  if (T.kw == 1) {
-    if (P.n_cols <= 2) DFX_FG(1, DFX_ARG(FastPolicy<2, 4>));
-    else if (P.n_cols <= 4) DFX_FG(1, DFX_ARG(FastPolicy<4, 4>));
-    else DFX_FG(1, DFX_ARG(FastPolicy<8, 2>));
-  } else {
-    if (P.n_cols <= 2) DFX_FG(2, DFX_ARG(FastPolicy<2, 4>));
-    else if (P.n_cols <= 4) DFX_FG(2, DFX_ARG(FastPolicy<4, 4>));
-    else DFX_FG(2, DFX_ARG(FastPolicy<8, 2>));
-  }
-#undef DFX_FG
-  return hipGetLastError();
 }
 
 }  // namespace dfx

@@ -137,10 +137,15 @@ static Pass1Choice select_pass1(const DevProgram& P, const DevFastPlan& fast, co
   // counts and padding either way, so the choice is made per launch.
   c.PT.flags &= ~PTF_WS;
   c.lds_bytes = partition_stage_bytes(c.PT);
-  const bool use_fast = fast.valid && !P.has_nulls;
-  c.unit = P.n_cols <= 2 ? (use_fast ? Pass1Unit::fast_c2 : Pass1Unit::interp_c2)
-           : P.n_cols <= 4 ? (use_fast ? Pass1Unit::fast_c4 : Pass1Unit::interp_c4)
-                           : (use_fast ? Pass1Unit::fast_c8 : Pass1Unit::interp_c8);
+  switch (choose_row_source(ScanKernel::pass1_generic, P, fast, T.kw, T.na, T.acc_kind, T.val_xform, false, 0)) {
+    case RowSource::fast_c2: c.unit = Pass1Unit::fast_c2; break;
+    case RowSource::fast_c4: c.unit = Pass1Unit::fast_c4; break;
+    case RowSource::fast_c8: c.unit = Pass1Unit::fast_c8; break;
+    case RowSource::interp_c2: c.unit = Pass1Unit::interp_c2; break;
+    case RowSource::interp_c4: c.unit = Pass1Unit::interp_c4; break;
+    case RowSource::interp_c8: c.unit = Pass1Unit::interp_c8; break;
+    default: break;  // (no other source in this ladder)
+  }
   return c;
 }
 

@@ -162,37 +162,31 @@ hipError_t launch_reduce(const DevProgram& P, const DevFastPlan& fast, const Dev
   if (n <= 0) return hipSuccess;
   Scope sc(KID_REDUCE, s, algo_bytes);
   const int grid = stream_grid((n + kBlock - 1) / kBlock, 8);
-#define DFX_REDUCE(POL, NM) hipLaunchKernelGGL((k_reduce<POL, NM>), dim3(grid), dim3(kBlock), 0, s, P, fast, C, plan, T, n, partial, ctrl)
-#define DFX_REDUCE_NA(POL) do { if (T.na <= 2) DFX_REDUCE(DFX_ARG(POL), 2); else DFX_REDUCE(DFX_ARG(POL), 8); } while (0)
-  // compile-time shape signatures first (dfx_sigs.hpp), then the run-time decoded fast plan, then
-  // the generic interpreter
-  if (sig_matches<SigCountPred2F64>(P, fast, 0, T.na, T.acc_kind, T.val_xform)) {
-    DFX_REDUCE(DFX_ARG(StaticPolicy<2, 8, SigCountPred2F64>), 2);
-    return hipGetLastError();
-  }
-  if (sig_matches<SigSumCountPred2F64>(P, fast, 0, T.na, T.acc_kind, T.val_xform)) {
-    DFX_REDUCE(DFX_ARG(StaticPolicy<2, 8, SigSumCountPred2F64>), 2);
-    return hipGetLastError();
-  }
-  if (P.has_nulls || !P.wide8 || (fast.plan_mode & 3) == 2) {  // validity bitmaps / 4-byte columns: the scan plan (see table_hash_agg)
-    DevFastPlan fp;
-    DevColumns cp;
-    if (bind_scan_plan(P, fast, C, 0, T.na, T.val_xform, false, &fp, &cp)) {
-#define DFX_REDUCE_P(POL, NM) hipLaunchKernelGGL((k_reduce<POL, NM>), dim3(grid), dim3(kBlock), 0, s, P, fp, cp, plan, T, n, partial, ctrl)
-      if (fp.scan.n_cols <= 2) { if (T.na <= 2) DFX_REDUCE_P(DFX_ARG(PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>), 2); else DFX_REDUCE_P(DFX_ARG(PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>), 8); }
-      else { if (T.na <= 2) DFX_REDUCE_P(DFX_ARG(PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>), 2); else DFX_REDUCE_P(DFX_ARG(PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>), 8); }
-#undef DFX_REDUCE_P
-      return hipGetLastError();
+  const BoundRowSource b = bind_row_source(ScanKernel::reduce, P, fast, C, 0, T.na, T.acc_kind, T.val_xform);
+  auto run = [&](auto pol) {
+    typedef typename decltype(pol)::type POL;
+    const DevFastPlan& F = b.F(fast);
+    const DevColumns& Cb = b.C(C);
+    if (POL::kIsStatic || T.na <= 2) {  // accumulators in registers: 2 or 8 (the signatures have at most two)
+      hipLaunchKernelGGL((k_reduce<POL, 2>), dim3(grid), dim3(kBlock), 0, s, P, F, Cb, plan, T, n, partial, ctrl);
+    } else if constexpr (!POL::kIsStatic) {
+      hipLaunchKernelGGL((k_reduce<POL, 8>), dim3(grid), dim3(kBlock), 0, s, P, F, Cb, plan, T, n, partial, ctrl);
     }
+    return hipGetLastError();
+  };
+  switch (b.source) {
+    case RowSource::sig_count_pred2_f64: return run(Policy<StaticPolicy<2, 8, SigCountPred2F64>>{});
+    case RowSource::sig_sum_count_pred2_f64: return run(Policy<StaticPolicy<2, 8, SigSumCountPred2F64>>{});
+    case RowSource::plan_c2: return run(Policy<PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>{});
+    case RowSource::plan_c4: return run(Policy<PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>{});
+    case RowSource::fast_c2: return run(Policy<FastPolicy<2, 8>>{});
+    case RowSource::fast_c4: return run(Policy<FastPolicy<4, 4>>{});
+    case RowSource::fast_c8: return run(Policy<FastPolicy<8, 2>>{});
+    case RowSource::interp_c2: return run(Policy<InterpPolicy<2, 8>>{});
+    case RowSource::interp_c4: return run(Policy<InterpPolicy<4, 4>>{});
+    case RowSource::interp_c8: return run(Policy<InterpPolicy<8, 2>>{});
+    default: return hipErrorNotSupported;  // (the host fused a predicate over nulls counting on a plan)
   }
-  if (fast.plan_mode & 4) return hipErrorNotSupported;  // (the host fused a predicate over nulls counting on a plan)
-  const bool use_fast = fast.valid && !P.has_nulls;
-  if (P.n_cols <= 2) { if (use_fast) DFX_REDUCE_NA(DFX_ARG(FastPolicy<2, 8>)); else DFX_REDUCE_NA(DFX_ARG(InterpPolicy<2, 8>)); }
-  else if (P.n_cols <= 4) { if (use_fast) DFX_REDUCE_NA(DFX_ARG(FastPolicy<4, 4>)); else DFX_REDUCE_NA(DFX_ARG(InterpPolicy<4, 4>)); }
-  else { if (use_fast) DFX_REDUCE_NA(DFX_ARG(FastPolicy<8, 2>)); else DFX_REDUCE_NA(DFX_ARG(InterpPolicy<8, 2>)); }
-#undef DFX_REDUCE_NA
-#undef DFX_REDUCE
-  return hipGetLastError();
 }
 
 }  // namespace dfx

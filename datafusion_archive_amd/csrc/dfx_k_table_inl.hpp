@@ -374,38 +374,28 @@ hipError_t table_hash_agg(const DevProgram& P, const DevFastPlan& fast, const De
   // LDS-heavy blocks: fewer, longer-lived workgroups amortise the cache init + flush
   const int per_cu = lds_bytes > 0 ? (lds_bytes > 40 * 1024 ? 2 : 4) : 8;
   const int grid = stream_grid(n_blocks, per_cu);
-#define DFX_HA(POL) hipLaunchKernelGGL((k_hash_agg<KW, POL>), dim3(grid), dim3(kBlock), lds_bytes, s, P, fast, C, plan, T, spill, n)
-  if (KW == 1 && sig_matches<SigKeySumPred2F64>(P, fast, KW, T.na, T.acc_kind, T.val_xform)) {
-    DFX_HA(DFX_ARG(StaticPolicy<2, 4, SigKeySumPred2F64>));
+  // (A scan plan where the decoded shapes would not run -- validity bitmaps -- or would run their slow loader -- 4-byte columns:
+  // the same shape family with nulls by arrow's rules and widening loads.  8-byte null-free scans keep FastPolicy here: it also
+  // takes product arguments; the partitioned strategy is where the rows are, and it runs plans for everything.)
+  const BoundRowSource b = bind_row_source(ScanKernel::hash_agg, P, fast, C, KW, T.na, T.acc_kind, T.val_xform);
+  auto run = [&](auto pol) {
+    hipLaunchKernelGGL((k_hash_agg<KW, typename decltype(pol)::type>), dim3(grid), dim3(kBlock), lds_bytes, s, P, b.F(fast), b.C(C), plan, T, spill, n);
     return hipGetLastError();
+  };
+  switch (b.source) {  // (every key width holds every kernel: a signature's rung is tried at its own width only)
+    case RowSource::sig_key_sum_pred2_f64: return run(Policy<StaticPolicy<2, 4, SigKeySumPred2F64>>{});
+    case RowSource::sig_key_sum: return run(Policy<StaticPolicy<2, 4, SigKeySum>>{});
+    case RowSource::sig_q1: return run(Policy<StaticPolicy<8, 2, SigQ1>>{});
+    case RowSource::plan_c2: return run(Policy<PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>{});
+    case RowSource::plan_c4: return run(Policy<PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>{});
+    case RowSource::fast_c2: return run(Policy<FastPolicy<2, 4>>{});
+    case RowSource::fast_c4: return run(Policy<FastPolicy<4, 4>>{});
+    case RowSource::fast_c8: return run(Policy<FastPolicy<8, 2>>{});
+    case RowSource::interp_c2: return run(Policy<InterpPolicy<2, 4>>{});
+    case RowSource::interp_c4: return run(Policy<InterpPolicy<4, 4>>{});
+    case RowSource::interp_c8: return run(Policy<InterpPolicy<8, 2>>{});
+    default: return hipErrorNotSupported;  // (the host fused a predicate over nulls counting on a plan)
   }
-  if (KW == 1 && sig_matches<SigKeySum>(P, fast, KW, T.na, T.acc_kind, T.val_xform)) {
-    DFX_HA(DFX_ARG(StaticPolicy<2, 4, SigKeySum>));
-    return hipGetLastError();
-  }
-  if (KW == 2 && sig_matches<SigQ1>(P, fast, KW, T.na, T.acc_kind, T.val_xform)) {
-    DFX_HA(DFX_ARG(StaticPolicy<8, 2, SigQ1>));
-    return hipGetLastError();
-  }
-  // A scan plan where the decoded shapes would not run (validity bitmaps) or would run their slow loader (4-byte columns):
-  // the same shape family with nulls by arrow's rules and widening loads.  (8-byte null-free scans keep FastPolicy here: it
-  // also takes product arguments; the partitioned strategy is where the rows are, and it runs plans for everything.)
-  if (P.has_nulls || !P.wide8 || (fast.plan_mode & 3) == 2) {
-    DevFastPlan fp;
-    DevColumns cp;
-    if (bind_scan_plan(P, fast, C, KW, T.na, T.val_xform, false, &fp, &cp)) {
-      if (fp.scan.n_cols <= 2) hipLaunchKernelGGL((k_hash_agg<KW, PlanPolicyN<2, 4, kPlanW4 | kPlanNulls>>), dim3(grid), dim3(kBlock), lds_bytes, s, P, fp, cp, plan, T, spill, n);
-      else hipLaunchKernelGGL((k_hash_agg<KW, PlanPolicyN<4, 2, kPlanW4 | kPlanNulls>>), dim3(grid), dim3(kBlock), lds_bytes, s, P, fp, cp, plan, T, spill, n);
-      return hipGetLastError();
-    }
-  }
-  if (fast.plan_mode & 4) return hipErrorNotSupported;  // (the host fused a predicate over nulls counting on a plan)
-  const bool use_fast = fast.valid && !P.has_nulls;
-  if (P.n_cols <= 2) { if (use_fast) DFX_HA(DFX_ARG(FastPolicy<2, 4>)); else DFX_HA(DFX_ARG(InterpPolicy<2, 4>)); }
-  else if (P.n_cols <= 4) { if (use_fast) DFX_HA(DFX_ARG(FastPolicy<4, 4>)); else DFX_HA(DFX_ARG(InterpPolicy<4, 4>)); }
-  else { if (use_fast) DFX_HA(DFX_ARG(FastPolicy<8, 2>)); else DFX_HA(DFX_ARG(InterpPolicy<8, 2>)); }
-#undef DFX_HA
-  return hipGetLastError();
 }
 
 template <int KW>

@@ -1260,6 +1260,14 @@ DEV void acc_atomic(uint8_t kind, uint64_t* p, uint64_t v) {
 }
 
 DEV uint64_t shfl_xor_u64(uint64_t v, int m) { return (uint64_t)__shfl_xor((unsigned long long)v, m, 64); }
+DEV uint64_t wave_inclusive_scan(uint64_t v) {  // (the scans of dfx_k_core.hip and k_compact of dfx_k_filter.hip)
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t o = __shfl_up(v, d, 64);
+    if (lane_id() >= d) v += o;
+  }
+  return v;
+}
 
 // ---------------------------------------------------------------------------------------------
 // group table: find-or-insert + atomic update

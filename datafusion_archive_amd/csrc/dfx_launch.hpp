@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "dfx_kernels.hpp"
+#include "dfx_row_source.hpp"
 
 namespace dfx {
 
@@ -22,7 +23,28 @@ struct Scope {
 // several times over (>> 256 WGs; blocks land round-robin on the 8 XCDs), capped so the
 // grid-stride loop amortises launch and tail effects.
 int stream_grid(int64_t units, int per_cu);
-#define DFX_ARG(...) __VA_ARGS__  // protects template commas inside macro arguments
+
+// One launch's row source (dfx_row_source.hpp) with the bindings that go with it: ask, bind the scan plan if asked, choose.
+// A plan_* source reads the plan's own fast plan and columns, every other the caller's: F() / C() are the one place that says so.
+struct BoundRowSource {
+  RowSource source = RowSource::none;
+  DevFastPlan fp;
+  DevColumns cp;
+  const DevFastPlan& F(const DevFastPlan& fast) const { return is_plan(source) ? fp : fast; }
+  const DevColumns& C(const DevColumns& cols) const { return is_plan(source) ? cp : cols; }
+};
+inline BoundRowSource bind_row_source(ScanKernel kernel, const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, int kw, int na,
+                                      const uint8_t* acc_kind, const uint8_t* val_xform) {
+  BoundRowSource b;
+  const bool bound = wants_scan_plan(kernel, P, fast) && bind_scan_plan(P, fast, C, kw, na, val_xform, false, &b.fp, &b.cp);
+  b.source = choose_row_source(kernel, P, fast, kw, na, acc_kind, val_xform, bound, bound ? b.fp.scan.n_cols : 0);
+  return b;
+}
+// hands a policy type to a launcher's generic lambda: run(Policy<FastPolicy<2, 8>>{})
+template <typename POL>
+struct Policy {
+  typedef POL type;
+};
 
 // group-table kernels, one explicit instantiation per key width (dfx_k_table{1,2,3,4}.hip)
 template <int KW>
