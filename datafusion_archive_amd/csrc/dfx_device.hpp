@@ -154,7 +154,7 @@ struct DevFastPlan {
   int32_t plan_mode; // AggOptions::plan as the launchers see it (scan.plan), bits 0..1: 0 never bind a scan plan, 1 after the
                      // signatures, 2 before them; bit 2: the host RELIES on the plan (a fused predicate over a batch with nulls, which
                      // only a plan evaluates by the reference's rules): a launcher that cannot bind one fails instead of falling back
-  DevScanPlan scan;  // filled per launch by bind_scan_plan() (dfx_expr.cpp) when a PlanPolicy kernel runs
+  DevScanPlan scan;  // filled per launch by bind_scan_plan() (dfx_scan_plan.hpp) when a PlanPolicy kernel runs
 };
 
 // ---- aggregation ----------------------------------------------------------------------------

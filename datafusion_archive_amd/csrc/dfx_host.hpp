@@ -318,8 +318,12 @@ void explain_line(std::string* out, int depth, const std::string& text);
 // "program: c columns, i instructions, l literals"
 std::string explain_program(const DevProgram& P);
 
-// ---- expressions (dfx_expr.cpp) ---------------------------------------------------------------
+// ---- expressions (dfx_expr.cpp: texts, validation, C ABI; dfx_expr_program.cpp: ProgramBuilder; dfx_expr_utf8.cpp: Utf8Terms) ----
 enum AggregateType { AGG_MIN = 0, AGG_MAX = 1, AGG_SUM = 2, AGG_COUNT = 3, AGG_AVG = 4, AGG_COUNT_DISTINCT = 5 };
+// dfx_expr.cpp, for its two siblings: Rust {:?} of an Operator and of an Expr; Rust `as` on a canonical 64-bit value
+const char* op_debug(int op);
+std::string expr_debug(const std::vector<dfx_expr_node>& nodes, int32_t idx);
+uint64_t host_cast_value(int from, int to, uint64_t v);
 
 }  // namespace dfx
 
@@ -375,7 +379,7 @@ class ProgramBuilder {
   Status bind(const DeviceBatch& batch, DevProgram* prog, DevColumns* cols) const;
   // Derive the shape-specialised plan (dfx_device.hpp: DevFastPlan) from the SSA program: pred is a
   // conjunction of `column <op> literal`, keys are plain columns, arguments are a column or a product
-  // of up to three (column | literal +- column | column * literal) factors.  F->valid = 0 otherwise.
+  // of up to three (column | literal +- column | column * literal) factors.  F->valid = 0 otherwise.  (dfx_scan_plan.hpp)
   void build_fast(uint8_t pred, const uint8_t* keys, int kw, const uint8_t* args, int na, DevFastPlan* F) const;
 
  private:
@@ -385,7 +389,7 @@ class ProgramBuilder {
   std::vector<int> cols_;
 };
 
-// Utf8 string terms of a predicate (deviation D9; dfx_expr.cpp).  A string term -- `Utf8 column <op> Utf8 literal` for Eq ..
+// Utf8 string terms of a predicate (deviation D9; dfx_expr_utf8.cpp).  A string term -- `Utf8 column <op> Utf8 literal` for Eq ..
 // GtEq with the literal on either side, `Utf8 column LIKE / NOT LIKE Utf8 literal` -- is evaluated by a kernel of its own
 // (dfx_k_utf8pred.hip) into a bitmap that the fused program reads as a VIRTUAL Boolean column appended after the input
 // schema's columns: the device-dictionary mechanism of Utf8 GROUP BY keys applied to predicates.  Identical terms share a column.

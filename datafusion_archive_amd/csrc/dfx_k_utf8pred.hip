@@ -1,6 +1,6 @@
 // dfx_k_utf8pred.hip -- Utf8 string terms on the device (deviation D9): `Utf8 column <op> Utf8 literal` for the six
 // comparisons and LIKE / NOT LIKE, one term over one batch into an Arrow LSB bitmap.  The operators bind that bitmap to the
-// fused programs as a virtual Boolean column (dfx_expr.cpp: Utf8Terms), the way a Utf8 GROUP BY key reaches them as a
+// fused programs as a virtual Boolean column (dfx_expr_utf8.cpp: Utf8Terms), the way a Utf8 GROUP BY key reaches them as a
 // virtual id column; a predicate that is one term uses the bitmap as the filter's mask directly.
 //
 // Shape (the one k_csv_parse settled on): one wave owns a tile of 64 rows and its ballot is the tile's bitmap word.  The

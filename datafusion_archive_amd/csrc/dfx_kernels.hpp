@@ -52,7 +52,7 @@ bool profile_get(int index, const char** name, int64_t* launches, double* total_
 
 int device_cu_count();
 
-// ---- scan plans (DevScanPlan, dfx_device.hpp; built in dfx_expr.cpp) -------------------------------------------------
+// ---- scan plans (DevScanPlan, dfx_device.hpp; built in dfx_scan_plan.hpp) -----------------------------------------------
 // Shape check at operator-creation time (no batch needed): <= 4 columns of 4 / 8-byte numeric types, a conjunction of
 // `column <op> literal` terms, plain-column keys, plain-column arguments.
 bool scan_plan_shape_ok(const DevProgram& P, const DevFastPlan& F, int kw, int na, const uint8_t* val_xform);

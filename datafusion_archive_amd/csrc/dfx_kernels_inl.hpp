@@ -1123,6 +1123,7 @@ struct PlanPolicy {
       return y0 ^ ((y0 ^ y1) & M1);
     }
   }
+  // (the host restates the five lines from `hi` to `r`, for the CPU tests of the planner: plan_term_passes, dfx_scan_plan.hpp)
   static DEV bool pass(const DevProgram&, const DevFastPlan& F, uint8_t, const COLV&, uint32_t, const u64x16& reg, uint32_t rv,
                        const PREP& W) {
     uint32_t ok = 1u;

@@ -134,7 +134,7 @@ inline RowSource choose_row_source(ScanKernel kernel, const DevProgram& P, const
 }
 
 // The answer where there are no bound columns to try a plan on (fewgroup_supported, explain()): the plan counts as bound where
-// scan_plan_shape_ok (plan_shape_ok: the caller's, dfx_expr.cpp) says it can be built; it then has one slot per program column.
+// scan_plan_shape_ok (plan_shape_ok: the caller's, dfx_scan_plan.hpp) says it can be built; it then has one slot per program column.
 inline RowSource row_source_without_batch(ScanKernel kernel, const DevProgram& P, const DevFastPlan& fast, int kw, int na,
                                           const uint8_t* acc_kind, const uint8_t* val_xform, bool plan_shape_ok) {
   const bool bound = wants_scan_plan(kernel, P, fast) && (fast.plan_mode & 3) != 0 && plan_shape_ok;

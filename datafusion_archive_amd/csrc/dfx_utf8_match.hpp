@@ -4,7 +4,7 @@
 //
 // Ordering is Rust `str` ordering: unsigned byte-wise lexicographic, a proper prefix sorts first.  Equality is byte equality.
 // LIKE: `%` any run of bytes (also none), `_` exactly one UTF-8 encoded character (a lead byte and its continuation bytes),
-// no escape character, anchored at both ends.  A pattern is compiled ONCE (utf8_compile_term in dfx_expr.cpp, host) into a class and a table
+// no escape character, anchored at both ends.  A pattern is compiled ONCE (utf8_compile_term in dfx_expr_utf8.cpp, host) into a class and a table
 // of `%`-separated segments; the first segment is anchored at the start, the last at the end, the middle ones are matched
 // leftmost-first -- exact for this pattern language (a segment has a fixed number of characters), so nothing backtracks.
 #pragma once

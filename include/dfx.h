@@ -457,7 +457,8 @@ int32_t dfx_aggregate_exchange(struct ArrowArrayStream* agg, dfx_comm* comm, int
 uint64_t dfx_debug_group_hash(uint64_t key);
 uint32_t dfx_debug_unhash32(uint32_t image);
 /* One `column <op> literal` term of a scan plan (csrc/dfx_device.hpp: DevScanPlan) evaluated on the host with the arithmetic
- * the kernels use: the range test on the order-preserving image of `value`.  dtype: the column's dfx_dtype (Int32, UInt32,
+ * the kernels use: the range test on the order-preserving image of `value` (csrc/dfx_scan_plan.hpp: plan_term_range and
+ * plan_term_passes; the entry point is in csrc/dfx_expr_program.cpp).  dtype: the column's dfx_dtype (Int32, UInt32,
  * Float32, Int64, UInt64, Float64); op: dfx_operator 0..5 (Eq NotEq Lt LtEq Gt GtEq); literal / value: canonical 64-bit
  * forms (signed ints sign-extended, unsigned zero-extended, Float32 bits in the low word, Float64 bits); is_null: the value
  * is null (arrow 0.12's rule for None decides).  Returns 0 / 1, or -1 for a type the plans do not cover.  Host code, no
