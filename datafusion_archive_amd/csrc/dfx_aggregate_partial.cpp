@@ -209,7 +209,7 @@ Status AggregateRelation::ungrouped_select_chunk(int c) {
   return Status::OK();
 }
 
-static uint64_t host_wrap_to(uint8_t t, uint64_t x) {  // == wrap_to (dfx_kernels_inl.hpp)
+static uint64_t host_wrap_to(uint8_t t, uint64_t x) {  // == wrap_to (dfx_k_base_inl.hpp)
   switch (t) {
     case DFX_INT8: return (uint64_t)(int64_t)(int8_t)x;
     case DFX_INT16: return (uint64_t)(int64_t)(int16_t)x;

@@ -107,7 +107,7 @@ struct DevFastArg {
 //   * validity bitmaps are read one BYTE per lane (the 64 lanes of a row group share 8 or 9 bytes: one cache line), the bit
 //     is (byte >> ((bit_offset + lane) & 7)) & 1; a column without a bitmap points at a block of 0xFF bytes.  A null value
 //     gives the term arrow 0.12's answer for None (it sorts below every value): DevPlanTerm::if_null;
-//   * the plan words live in VECTOR registers (dfx_kernels_inl.hpp, PlanPolicy): no scalar-register pressure, no selects.
+//   * the plan words live in VECTOR registers (dfx_k_plan_policy_inl.hpp, PlanPolicy): no scalar-register pressure, no selects.
 // Column slots are the plan's own: PlanPolicy1 kernels (one key, one routed value) find the key in slot 0 and the
 // aggregate's argument in slot 1, further predicate columns behind them.
 constexpr int kPlanCols = 4;

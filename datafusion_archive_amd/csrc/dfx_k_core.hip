@@ -18,7 +18,8 @@
 
 #include <algorithm>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

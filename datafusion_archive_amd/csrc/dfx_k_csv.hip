@@ -18,7 +18,7 @@
 // Bound: HBM reads of the text (2 boundary passes, 3 where there are quotes, + 1..2 cell passes); ingest is PCIe-bound
 // (63 GB/s) long before that matters.
 #include "dfx_csv_walk.hpp"
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 #include "dfx_numparse.hpp"
 

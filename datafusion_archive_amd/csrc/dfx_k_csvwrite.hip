@@ -10,7 +10,7 @@
 #include <algorithm>
 
 #include "dfx_csvwrite.hpp"
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 #include "dfx_numfmt.hpp"
 

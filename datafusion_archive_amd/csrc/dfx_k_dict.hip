@@ -12,7 +12,7 @@
 // group table stay valid.
 #include <algorithm>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

@@ -6,7 +6,9 @@
 // spill list, the growth (k_rehash) and the spill replay (k_merge_rows) are the group table's own helpers; what is new here is
 // the evaluation of the tuple, the skipping of null arguments, the float canonicalisation and the two emit kernels.
 #pragma once
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_plan_policy_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

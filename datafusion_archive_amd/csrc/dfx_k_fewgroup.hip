@@ -18,7 +18,9 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_plan_policy_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

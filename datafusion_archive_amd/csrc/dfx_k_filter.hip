@@ -8,7 +8,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

@@ -30,7 +30,7 @@
 // PQ_ERR_* bit in the control block's CTRL_ERROR word (error_from_ctrl: DFX_PARSER_ERROR) and the slot gets 0.  Values of a page
 // start at an arbitrary byte: a value is loaded in one access only where its address is aligned, byte by byte otherwise.
 #include "../../include/dfx.h"
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 #include "dfx_parquet_rle.hpp"
 

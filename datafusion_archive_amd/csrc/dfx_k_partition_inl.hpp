@@ -23,7 +23,9 @@
 // launch_partition), dfx_pass1_layout.hpp the kernels' LDS bytes and the choice of the routed layout, dfx_k_pass2.hip pass 2 (its
 // forms and their choice: dfx_pass2_forms.hpp).
 #pragma once
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_plan_policy_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 #include "dfx_pass1_layout.hpp"
 #include "dfx_pass1_units.hpp"

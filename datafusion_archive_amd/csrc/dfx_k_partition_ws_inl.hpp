@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
   // chunk geometry: rows per chunk (= per 128-byte line), rows per ring, dwords per row
   // R8 (PTF_ROW8, a policy over both shadows): 8-byte rows {image, Float32 bits}, sixteen per line; the queues' operand plane holds
   // the 4-byte shadow words (the plane's other half stays unused: partition_ws_bytes counts 4 bytes per queue row less)
-  constexpr bool R8 = Row8Of<POL>::value;
+  constexpr bool R8 = POL::kRow8;
   static_assert(!R8 || (NV == 1 && kNarrowLine), "one routed operand, whole-line chunks");
   constexpr int CH = NV == 2 ? kPairChunkRows : R8 ? kRow8ChunkRows : kWsCH, RP = NV == 2 ? kPairRingRows : R8 ? kRow8RingRows : kWsRP,
                 DW = NV == 2 ? kPairRowDwords : R8 ? kRow8Dwords : 3;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
             COLV cur = col[u];
             const uint32_t curv = cv[u];
             bool inb = true;
-            if constexpr (RowPairsOf<POL>::value) {  // (key and operand pair words: StaticKey4Val4Policy -- the lane's own two rows of the pair)
+            if constexpr (POL::kRowPairs) {  // (key and operand pair words: StaticKey4Val4Policy -- the lane's own two rows of the pair)
               cur = POL::pair_row(col[u & ~1], u & 1);
               if constexpr (!FULL) inb = w0 * 64 + POL::trip_row(u, lane) < n;
             } else {
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kRingBlock) void k_partition_ws(const DevProgram P,
             uint64_t pm = POL::template pass_mask<FORM>(P, F, plan.pred, cur, curv, reg, rv, prep);  // (evaluated for every lane)
             if constexpr (!FULL) pm &= __ballot(inb);
             uint64_t key;
-            if constexpr (KeyPairsOf<POL>::value) key = POL::pair_key(col[u & ~1], u & 1, lane);  // (two keys per lane: StaticKey4Policy)
+            if constexpr (POL::kKeyPairs) key = POL::pair_key(col[u & ~1], u & 1, lane);  // (two keys per lane: StaticKey4Policy)
             else key = POL::key(P, F, plan.key[0], 0, cur, curv, reg, rv);
             uint64_t v;
             bool valid;

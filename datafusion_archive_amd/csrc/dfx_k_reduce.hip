@@ -1,7 +1,9 @@
 // dfx_k_reduce.hip -- K5 reduce_all (ungrouped aggregates), its own translation unit.
 #include <type_traits>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_plan_policy_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

@@ -15,7 +15,7 @@
 // Bound: HBM / store transactions (8 B + 4 B scattered per element and pass).
 #include <algorithm>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

@@ -1,7 +1,9 @@
 // dfx_k_table_inl.hpp -- the group-table kernels, templated on the number of key words KW.
 // Instantiated once per KW in dfx_k_table{1,2,3,4}.hip so the four variants build in parallel.
 #pragma once
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_acc_inl.hpp"
+#include "dfx_k_plan_policy_inl.hpp"
+#include "dfx_k_policy_inl.hpp"
 #include "dfx_launch.hpp"
 
 namespace dfx {

@@ -20,7 +20,7 @@
 // column's owner allocated around the bytes it references.
 #include <algorithm>
 
-#include "dfx_kernels_inl.hpp"
+#include "dfx_k_base_inl.hpp"
 #include "dfx_launch.hpp"
 #include "dfx_utf8_match.hpp"
 

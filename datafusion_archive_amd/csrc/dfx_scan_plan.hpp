@@ -206,11 +206,11 @@ inline void plan_term_range(uint8_t dtype, uint8_t m, bool ne, uint64_t imm, Dev
   T->span = hi - lo;
   T->inv = inv ? 1u : 0u;
   // arrow 0.12 bool_op compares Option<T>: None sorts below every value, the result is never null (expression.rs:171-210
-  // -> array_ops; restated in run_program, dfx_kernels_inl.hpp).  For `null <op> literal`:
+  // -> array_ops; restated in run_program, dfx_k_interp_inl.hpp).  For `null <op> literal`:
   T->if_null = ne ? 1u : (m == 1 || m == 3) ? 1u : 0u;
 }
 
-// What a lane makes of a non-null value under a term: PlanPolicy::pass (dfx_kernels_inl.hpp, the five lines from `hi` to `r`)
+// What a lane makes of a non-null value under a term: PlanPolicy::pass (dfx_k_plan_policy_inl.hpp, the five lines from `hi` to `r`)
 // restated word for word, with the three flag bits of PlanPolicy::prepare it reads (bit 0: T.a != 0, bit 1: T.b >> 63, bit 2:
 // T.inv) taken from the term itself.  x: the value widened to 64 bits, as PlanPolicy::eval leaves it in the row's register.
 // The kernel's form is tuned (flag word, sbfe) and stays its own; tests/native/scan_plan_check.cpp and

@@ -4,7 +4,7 @@
 // A signature fixes everything about a scan that does not depend on the data: how many 8-byte
 // columns it reads, the predicate terms (type + column slot), the key columns, and for each
 // aggregate its argument column, accumulator kind and operand transform.  Only the comparison
-// operators and the literals stay run-time values.  StaticPolicy<.., SIG> (dfx_kernels_inl.hpp)
+// operators and the literals stay run-time values.  StaticPolicy<.., SIG> (dfx_k_policy_inl.hpp)
 // turns a signature into straight-line code with no dtype / kind switches at all; a plan that
 // matches no signature runs FastPolicy (same shape family, decoded at run time) or the interpreter.
 //

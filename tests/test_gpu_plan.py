@@ -1,4 +1,4 @@
-"""Scan plans on the device (csrc/dfx_device.hpp: DevScanPlan; PlanPolicy in csrc/dfx_kernels_inl.hpp): the run-time query
+"""Scan plans on the device (csrc/dfx_device.hpp: DevScanPlan; PlanPolicy in csrc/dfx_k_plan_policy_inl.hpp): the run-time query
 shapes -- any single MIN / MAX / COUNT / SUM, one to four `column <op> literal` terms over Int32 ... Float64 columns,
 4-byte keys, validity bitmaps on any referenced column -- evaluated as data by the same kernels, against the CPU oracle
 (reference-shaped, 1024-row batches) group by group and bit for bit.  Sizes are chosen so that the automatic strategy

@@ -68,7 +68,7 @@ def test_plan_terms_on_random_doubles_and_integers():
 
 def test_plan_terms_null_values_follow_arrow_0_12():
     """bool_op compares Option<T>: None sorts below every value and the result is never null (oracle/dfx_oracle.c
-    compare_arrays; the device interpreter's table in dfx_kernels_inl.hpp): null == x false, != true, < true, <= true,
+    compare_arrays; the device interpreter's table in dfx_k_interp_inl.hpp): null == x false, != true, < true, <= true,
     > false, >= false -- whatever the literal."""
     L = _ffi.lib()
     want = {"eq": 0, "ne": 1, "lt": 1, "le": 1, "gt": 0, "ge": 0}
