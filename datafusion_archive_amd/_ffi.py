@@ -77,7 +77,7 @@ EXPORTED_SYMBOLS = [
     "dfx_profile_enable", "dfx_profile_reset", "dfx_profile_count", "dfx_profile_get", "dfx_set_option",
     "dfx_counter_get", "dfx_counter_reset", "dfx_relation_explain", "dfx_relation_drain_device", "dfx_filter_debug_mask",
     "dfx_debug_group_hash", "dfx_debug_unhash32", "dfx_debug_plan_term", "dfx_debug_utf8_term",
-    "dfx_csv_write", "dfx_debug_format_value", "dfx_parquet_datasource_new",
+    "dfx_csv_write", "dfx_debug_format_value", "dfx_parquet_datasource_new", "dfx_parquet_write",
 ]
 
 _lib = None
@@ -186,6 +186,8 @@ def lib() -> ctypes.CDLL:
     L.dfx_debug_utf8_term.restype = ctypes.c_int32
     L.dfx_csv_write.argtypes = [P(ArrowArrayStream), ctypes.c_char_p, P(OptionC), ctypes.c_int32, P(ctypes.c_int64), P(ctypes.c_int64)] + c_err
     L.dfx_csv_write.restype = ctypes.c_int32
+    L.dfx_parquet_write.argtypes = [P(ArrowArrayStream), ctypes.c_char_p, P(OptionC), ctypes.c_int32, P(ctypes.c_int64), P(ctypes.c_int64)] + c_err
+    L.dfx_parquet_write.restype = ctypes.c_int32
     L.dfx_debug_format_value.argtypes = [ctypes.c_int32, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
     L.dfx_debug_format_value.restype = ctypes.c_int32
     L.dfx_counter_get.argtypes = [ctypes.c_char_p]

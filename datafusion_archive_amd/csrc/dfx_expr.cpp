@@ -37,6 +37,11 @@
 //       required / optional leaves of BOOLEAN, INT32 / INT64 with their Int annotations, FLOAT, DOUBLE and String byte arrays, from
 //       UNCOMPRESSED or LZ4_RAW chunks of dictionary, V1 and V2 pages in PLAIN, RLE_DICTIONARY and RLE; anything else is NotImplemented at
 //       construction.  Parity unpinned; the contract is pyarrow's reader.
+//   D13 The Parquet sink (PhysicalPlan::Write { plan, filename, kind }, physicalplan.rs:24-29, with kind = FileType::Parquet,
+//       dfparser.rs:31-36: declared, never run): dfx_parquet_write (dfx_parquet_write.cpp) writes a flat schema of the twelve types in
+//       UNCOMPRESSED chunks of V1 PLAIN pages whose bodies are encoded on the device (dfx_k_parquet_write.hip); any other column
+//       type is NotImplemented before a file exists.  Parity unpinned; the contract: pyarrow and dfx_parquet_datasource_new read back
+//       the table that went in, bit for bit.
 #include <charconv>
 #include <string.h>
 #include <strings.h>

@@ -190,6 +190,12 @@ struct Counters {
   long long parquet_inflated_bytes = 0;          // bytes of inflated image produced (the pages' uncompressed sizes less V2's level prefixes)
   long long parquet_lz4_sequences = 0;           // LZ4 sequences the inflate kernel parsed (summed on the device)
   long long parquet_inflated_bytes_to_host = 0;  // bytes of inflated image copied back for the host's walk of BYTE_ARRAY length chains
+  // Parquet writer (dfx_parquet_write.cpp; tests/test_gpu_parquet_write.py): they observe, they decide nothing
+  long long parquet_write_pages = 0;                   // data pages written
+  long long parquet_write_bytes = 0;                   // bytes of the files written
+  long long parquet_write_rle_level_pages = 0;         // ... pages of OPTIONAL columns whose levels are one RLE run (all valid / all null)
+  long long parquet_write_bitpacked_level_pages = 0;   // ... whose levels are one bit-packed run (valid and null rows)
+  long long parquet_write_row_groups = 0;              // row groups written
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;

@@ -40,6 +40,7 @@ enum KernelId : int {
   KID_CSV_WRITE,
   KID_PARQUET,
   KID_PARQUET_INFLATE,
+  KID_PARQUET_WRITE,
   KID_COUNT_
 };
 const char* kernel_name(int kid);

@@ -1,0 +1,339 @@
+// dfx_parquet_enc.hpp -- what the Parquet writer's kernels (dfx_k_parquet_write.hip), its host code (dfx_parquet_write.cpp) and its
+// CPU test (tests/native/parquet_write_check.cpp) share (deviation D13).  Free of HIP.
+//
+//   geometry   rows -> row groups of exactly row_group_rows rows (the last shorter) -> PIECES (the rows of one input batch that fall
+//              into one group) -> PAGES of page_rows rows (the last of a piece shorter) -> TILES of 64 rows.  page_rows is a multiple
+//              of 64, so a tile never crosses a page; a page never holds rows of two batches.
+//   a page     V1 data page, PLAIN, UNCOMPRESSED: [definition levels, OPTIONAL columns only][values of the non-null rows, dense]
+//   levels     {u32 length}{one run of the RLE / bit-packed hybrid at width 1}: an RLE run of 1 when every row of the page is valid, an
+//              RLE run of 0 when none is, else one bit-packed run of ceil(n / 8) groups (= bytes), padding bits zero.  The page's own
+//              non-null count decides, never the batch's null_count.
+//   values     Boolean: bits, LSB first, ceil(non-nulls / 8) bytes; Int8 .. UInt32: sign / zero extended to 4 bytes; Int64, UInt64,
+//              Float32, Float64: as they are; Utf8: {u32 length}{bytes} per value
+//   i32 rule   a page body of 2^31 - 1 bytes or more is refused (the page header's sizes are i32)
+//
+// The formulae are DFX_PQ_HD (host and device); encode_page is the sequential restatement the kernels are held against (the GPU tests
+// compare whole files byte for byte), FileWriter lays pages out as a file: both sides write files with it.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/dfx.h"
+#include "dfx_parquet_rle.hpp"
+#include "dfx_parquet_thrift_write.hpp"
+
+namespace dfx {
+namespace pqw {
+
+constexpr int64_t kDefaultRowGroupRows = 1 << 20;
+constexpr int64_t kDefaultPageRows = 1 << 15;  // a choice: nothing has been measured
+constexpr int64_t kTileRows = 64;
+constexpr int64_t kLaunchRows = 1 << 20;  // rows of one launch chain: a whole number of pages, at most this many rows (one page if a page is larger)
+constexpr uint32_t kLongValue = 256;      // a Utf8 value longer than this is copied by the whole wave
+constexpr uint64_t kMaxBodyBytes = 0x7FFFFFFFull - 1;  // the largest body a page header can describe and this writer accepts
+
+enum : uint32_t { LEVELS_NONE = 0, LEVELS_ALL_VALID = 1, LEVELS_ALL_NULL = 2, LEVELS_MIXED = 3 };
+
+// ---- options and geometry ----------------------------------------------------------------------------------------------------------
+// (a page header counts its values in an i32: 2^30 rows is the largest page the writer takes)
+DFX_PQ_HD bool page_rows_ok(int64_t page_rows) { return page_rows >= kTileRows && page_rows % kTileRows == 0 && page_rows <= (1ll << 30); }
+DFX_PQ_HD bool row_group_rows_ok(int64_t rows) { return rows >= 1; }
+DFX_PQ_HD int64_t launch_rows(int64_t page_rows) { return page_rows >= kLaunchRows ? page_rows : kLaunchRows / page_rows * page_rows; }
+DFX_PQ_HD int64_t pages_of(int64_t rows, int64_t page_rows) { return (rows + page_rows - 1) / page_rows; }
+DFX_PQ_HD int64_t tiles_of(int64_t rows) { return (rows + kTileRows - 1) / kTileRows; }
+// rows of the piece that a batch contributes to a row group that already holds `filled` rows, `left` rows of the batch remaining
+DFX_PQ_HD int64_t piece_rows(int64_t filled, int64_t left, int64_t row_group_rows) {
+  const int64_t room = row_group_rows - filled;
+  return left < room ? left : room;
+}
+
+// ---- per type ----------------------------------------------------------------------------------------------------------------------
+DFX_PQ_HD bool dtype_ok(int dtype) { return dtype >= DFX_BOOLEAN && dtype <= DFX_UTF8; }
+// bytes of a stored value; 0: Boolean (bits) and Utf8 (length-prefixed)
+DFX_PQ_HD uint32_t stored_width(int dtype) {
+  switch (dtype) {
+    case DFX_INT8:
+    case DFX_INT16:
+    case DFX_INT32:
+    case DFX_UINT8:
+    case DFX_UINT16:
+    case DFX_UINT32:
+    case DFX_FLOAT32: return 4;
+    case DFX_INT64:
+    case DFX_UINT64:
+    case DFX_FLOAT64: return 8;
+    default: return 0;
+  }
+}
+DFX_PQ_HD uint32_t source_width(int dtype) {
+  switch (dtype) {
+    case DFX_INT8:
+    case DFX_UINT8: return 1;
+    case DFX_INT16:
+    case DFX_UINT16: return 2;
+    case DFX_BOOLEAN:
+    case DFX_UTF8: return 0;
+    default: return stored_width(dtype);
+  }
+}
+// the stored image of a value whose source bytes are the low bytes of raw
+DFX_PQ_HD uint64_t widen(int dtype, uint64_t raw) {
+  switch (dtype) {
+    case DFX_INT8: return (uint64_t)(uint32_t)(int32_t)(int8_t)raw;
+    case DFX_INT16: return (uint64_t)(uint32_t)(int32_t)(int16_t)raw;
+    case DFX_UINT8: return raw & 0xFFull;
+    case DFX_UINT16: return raw & 0xFFFFull;
+    case DFX_INT32:
+    case DFX_UINT32:
+    case DFX_FLOAT32: return raw & 0xFFFFFFFFull;
+    default: return raw;
+  }
+}
+// bytes of a page's value block; utf8_bytes: the sum of 4 + length over the page's non-null rows
+DFX_PQ_HD uint64_t value_bytes(int dtype, uint64_t non_null, uint64_t utf8_bytes) {
+  if (dtype == DFX_UTF8) return utf8_bytes;
+  if (dtype == DFX_BOOLEAN) return (non_null + 7) / 8;
+  return non_null * stored_width(dtype);
+}
+
+// ---- the level block ---------------------------------------------------------------------------------------------------------------
+DFX_PQ_HD uint32_t varint_len(uint64_t v) {
+  uint32_t n = 1;
+  while (v >= 0x80) {
+    v >>= 7;
+    ++n;
+  }
+  return n;
+}
+DFX_PQ_HD uint32_t level_kind(bool optional, uint64_t n, uint64_t non_null) {
+  if (!optional) return LEVELS_NONE;
+  return non_null == n ? LEVELS_ALL_VALID : non_null == 0 ? LEVELS_ALL_NULL : LEVELS_MIXED;
+}
+// the run's header varint: count << 1 for an RLE run, groups << 1 | 1 for the bit-packed one
+DFX_PQ_HD uint64_t level_run_header(uint32_t kind, uint64_t n) { return kind == LEVELS_MIXED ? ((n + 7) / 8) << 1 | 1 : n << 1; }
+// bytes of the run: header + the value byte (RLE) or the groups (bit-packed)
+DFX_PQ_HD uint64_t level_run_bytes(uint32_t kind, uint64_t n) {
+  if (kind == LEVELS_NONE) return 0;
+  return varint_len(level_run_header(kind, n)) + (kind == LEVELS_MIXED ? (n + 7) / 8 : 1);
+}
+// bytes of the block: the 4-byte length and the run; 0 for a REQUIRED column
+DFX_PQ_HD uint64_t level_block_bytes(uint32_t kind, uint64_t n) { return kind == LEVELS_NONE ? 0 : 4 + level_run_bytes(kind, n); }
+// the block's first bytes -- length, run header, and for an RLE run its value byte -- as two little-endian words (byte k of the
+// block is byte k of *lo for k < 8, byte k - 8 of *hi beyond); returns how many (at most 4 + 5 + 1: n < 2^32).  A mixed page's
+// bitmap bytes follow at that byte of the block, 8 per tile.
+DFX_PQ_HD uint32_t level_block_prefix(uint32_t kind, uint64_t n, uint64_t* lo, uint64_t* hi) {
+  uint64_t w0 = level_run_bytes(kind, n) & 0xFFFFFFFFull, w1 = 0;
+  uint32_t k = 4;
+  uint64_t h = level_run_header(kind, n);
+  for (;;) {
+    const uint64_t b = h >= 0x80 ? ((h & 0x7F) | 0x80) : h;
+    if (k < 8) w0 |= b << (8 * k);
+    else w1 |= b << (8 * (k - 8));
+    ++k;
+    if (h < 0x80) break;
+    h >>= 7;
+  }
+  if (kind != LEVELS_MIXED) {
+    const uint64_t b = kind == LEVELS_ALL_VALID ? 1 : 0;
+    if (k < 8) w0 |= b << (8 * k);
+    else w1 |= b << (8 * (k - 8));
+    ++k;
+  }
+  *lo = w0;
+  *hi = w1;
+  return k;
+}
+
+// ---- the i32 size rule -------------------------------------------------------------------------------------------------------------
+DFX_PQ_HD bool body_fits(uint64_t level_bytes, uint64_t val_bytes) {
+  const uint64_t body = level_bytes + val_bytes;
+  return body >= level_bytes && body <= kMaxBodyBytes;
+}
+
+// ---- the tables between the kernels ------------------------------------------------------------------------------------------------
+struct PqwTile {       // per column and tile of a launch
+  uint32_t non_null;   // measure: valid rows of the tile
+  uint32_t rank_base;  // scan: valid rows of the page before the tile
+  uint64_t bytes;      // measure: Utf8: the sum of 4 + length over the tile's valid rows; else 0
+  uint64_t byte_base;  // scan: ... over the page's tiles before it
+};
+enum : uint32_t { PQW_PAGE_TOO_LARGE = 1u };
+struct PqwPage {         // per column and page of a launch: what the host reads back (scan; `base` by the bases kernel)
+  uint64_t base;         // of the body in the launch's output buffer, 8-byte aligned; entry [pages] holds the buffer's length
+  uint64_t val_bytes;
+  uint32_t level_bytes;  // 0: REQUIRED
+  uint32_t non_null;
+  uint32_t kind;         // LEVELS_*
+  uint32_t flags;        // PQW_PAGE_TOO_LARGE: the i32 rule refuses the page; it takes no room in the buffer
+};
+
+// ---- schema ------------------------------------------------------------------------------------------------------------------------
+inline LeafSchema leaf_schema(const std::string& name, int dtype, bool nullable) {
+  LeafSchema e;
+  e.name = name;
+  e.repetition = nullable ? REP_OPTIONAL : REP_REQUIRED;
+  auto integer = [&](int physical, int bits, bool is_signed, int converted) {
+    e.physical = physical;
+    e.logical = LOGICAL_INTEGER;
+    e.int_bits = bits;
+    e.int_signed = is_signed;
+    e.converted = converted;
+  };
+  switch (dtype) {
+    case DFX_BOOLEAN: e.physical = PHYS_BOOLEAN; break;
+    case DFX_INT8: integer(PHYS_INT32, 8, true, CONV_INT_8); break;
+    case DFX_INT16: integer(PHYS_INT32, 16, true, CONV_INT_16); break;
+    case DFX_INT32: integer(PHYS_INT32, 32, true, CONV_INT_32); break;
+    case DFX_UINT8: integer(PHYS_INT32, 8, false, CONV_UINT_8); break;
+    case DFX_UINT16: integer(PHYS_INT32, 16, false, CONV_UINT_16); break;
+    case DFX_UINT32: integer(PHYS_INT32, 32, false, CONV_UINT_32); break;
+    case DFX_INT64: e.physical = PHYS_INT64; break;
+    case DFX_UINT64: integer(PHYS_INT64, 64, false, CONV_UINT_64); break;
+    case DFX_FLOAT32: e.physical = PHYS_FLOAT; break;
+    case DFX_FLOAT64: e.physical = PHYS_DOUBLE; break;
+    default:
+      e.physical = PHYS_BYTE_ARRAY;
+      e.logical = LOGICAL_STRING;
+      e.converted = CONV_UTF8;
+  }
+  return e;
+}
+
+// ---- the sequential page encoder ---------------------------------------------------------------------------------------------------
+struct SourceColumn {  // Arrow buffers of one column, as DeviceColumn has them
+  int dtype = DFX_TYPE_NONE;
+  bool optional = true;
+  const uint8_t* validity = nullptr;  // null: every row is valid
+  int64_t bit_offset = 0;             // of row 0 in validity and in Boolean values
+  const void* values = nullptr;       // fixed width: row 0; Boolean: the bitmap's base
+  const int32_t* offsets = nullptr;   // Utf8: row 0 (rows + 1 entries)
+  const uint8_t* data = nullptr;      // Utf8: indexed by the raw offsets
+};
+struct EncodedPage {
+  int64_t num_values = 0, non_null = 0;
+  uint32_t kind = LEVELS_NONE;
+  uint64_t level_bytes = 0, val_bytes = 0;
+};
+inline bool source_bit(const uint8_t* bm, int64_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
+inline bool source_valid(const SourceColumn& c, int64_t row) { return !c.validity || source_bit(c.validity, c.bit_offset + row); }
+// rows [row0, row0 + n) of the column as one page body appended to *body.  false: the i32 rule refuses the page (nothing appended).
+inline bool encode_page(const SourceColumn& c, int64_t row0, int64_t n, std::vector<uint8_t>* body, EncodedPage* info) {
+  uint64_t non_null = 0, utf8 = 0;
+  for (int64_t r = row0; r < row0 + n; ++r) {
+    if (!source_valid(c, r)) continue;
+    ++non_null;
+    if (c.dtype == DFX_UTF8) utf8 += 4 + (uint64_t)(c.offsets[r + 1] - c.offsets[r]);
+  }
+  info->num_values = n;
+  info->non_null = (int64_t)non_null;
+  info->kind = level_kind(c.optional, (uint64_t)n, non_null);
+  info->level_bytes = level_block_bytes(info->kind, (uint64_t)n);
+  info->val_bytes = value_bytes(c.dtype, non_null, utf8);
+  if (!body_fits(info->level_bytes, info->val_bytes)) return false;
+  const size_t at = body->size();
+  body->resize(at + (size_t)(info->level_bytes + info->val_bytes), 0);
+  uint8_t* p = body->data() + at;
+  if (info->kind != LEVELS_NONE) {
+    uint64_t lo = 0, hi = 0;
+    const uint32_t len = level_block_prefix(info->kind, (uint64_t)n, &lo, &hi);
+    for (uint32_t k = 0; k < len; ++k) p[k] = (uint8_t)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xFF);
+    if (info->kind == LEVELS_MIXED)
+      for (int64_t i = 0; i < n; ++i)
+        if (source_valid(c, row0 + i)) p[len + (i >> 3)] |= (uint8_t)(1u << (i & 7));
+  }
+  uint8_t* v = p + info->level_bytes;
+  const uint32_t sw = stored_width(c.dtype), rw = source_width(c.dtype);
+  uint64_t rank = 0, at_byte = 0;
+  for (int64_t r = row0; r < row0 + n; ++r) {
+    if (!source_valid(c, r)) continue;
+    if (c.dtype == DFX_BOOLEAN) {
+      if (source_bit((const uint8_t*)c.values, c.bit_offset + r)) v[rank >> 3] |= (uint8_t)(1u << (rank & 7));
+    } else if (c.dtype == DFX_UTF8) {
+      const uint32_t len = (uint32_t)(c.offsets[r + 1] - c.offsets[r]);
+      for (int k = 0; k < 4; ++k) v[at_byte + k] = (uint8_t)(len >> (8 * k));
+      if (len) memcpy(v + at_byte + 4, c.data + c.offsets[r], len);
+      at_byte += 4 + (uint64_t)len;
+    } else {
+      uint64_t raw = 0;
+      memcpy(&raw, (const uint8_t*)c.values + (size_t)r * rw, rw);  // (little-endian hosts: what the library runs on)
+      const uint64_t w = widen(c.dtype, raw);
+      memcpy(v + rank * sw, &w, sw);
+    }
+    ++rank;
+  }
+  return true;
+}
+
+// ---- the file: magic, chunks page by page, footer ----------------------------------------------------------------------------------
+struct ColumnSpec {
+  std::string name;
+  int dtype = DFX_TYPE_NONE;
+  bool nullable = true;
+};
+inline const char* created_by() { return "datafusion_archive_amd dfx_parquet_write (D13)"; }
+
+// Pages go in row group by row group, column by column, in row order: begin_row_group, per column begin_chunk + add_page*, then
+// end_row_group.  `put` receives the file's bytes in order (false: the write failed; the writer stops and every later call fails).
+class FileWriter {
+ public:
+  typedef bool (*Put)(void* ctx, const void* p, size_t n);
+  FileWriter(std::vector<ColumnSpec> cols, Put put, void* ctx) : cols_(std::move(cols)), put_(put), ctx_(ctx) {}
+  bool begin() { return emit("PAR1", 4); }
+  void begin_row_group() { groups_.emplace_back(); }
+  void begin_chunk(size_t c) {
+    ChunkInfo k;
+    k.physical = leaf_schema(cols_[c].name, cols_[c].dtype, cols_[c].nullable).physical;
+    k.optional = cols_[c].nullable;
+    k.name = cols_[c].name;
+    k.data_page_offset = (int64_t)bytes_;
+    groups_.back().chunks.push_back(k);
+  }
+  bool add_page(int64_t num_values, int64_t non_null, const void* body, size_t body_bytes) {
+    header_.clear();
+    write_page_header((int32_t)body_bytes, (int32_t)num_values, &header_);
+    ChunkInfo& k = groups_.back().chunks.back();
+    k.num_values += num_values;
+    k.null_count += num_values - non_null;
+    k.total_size += (int64_t)(header_.size() + body_bytes);
+    ++pages_;
+    return emit(header_.data(), header_.size()) && emit(body, body_bytes);
+  }
+  void end_row_group(int64_t rows) {
+    groups_.back().num_rows = rows;
+    rows_ += rows;
+  }
+  bool finish() {
+    std::vector<LeafSchema> leaves;
+    for (const ColumnSpec& c : cols_) leaves.push_back(leaf_schema(c.name, c.dtype, c.nullable));
+    std::vector<uint8_t> footer;
+    write_file_meta(leaves, groups_, rows_, created_by(), &footer);
+    uint8_t tail[8];
+    for (int k = 0; k < 4; ++k) tail[k] = (uint8_t)((uint32_t)footer.size() >> (8 * k));
+    memcpy(tail + 4, "PAR1", 4);
+    return emit(footer.data(), footer.size()) && emit(tail, 8);
+  }
+  uint64_t bytes() const { return bytes_; }
+  int64_t pages() const { return pages_; }
+  int64_t row_groups() const { return (int64_t)groups_.size(); }
+
+ private:
+  bool emit(const void* p, size_t n) {
+    if (failed_ || (n && !put_(ctx_, p, n))) return !(failed_ = true);
+    bytes_ += n;
+    return true;
+  }
+  std::vector<ColumnSpec> cols_;
+  Put put_;
+  void* ctx_;
+  std::vector<RowGroupInfo> groups_;
+  std::vector<uint8_t> header_;
+  uint64_t bytes_ = 0;
+  int64_t rows_ = 0, pages_ = 0;
+  bool failed_ = false;
+};
+
+}  // namespace pqw
+}  // namespace dfx

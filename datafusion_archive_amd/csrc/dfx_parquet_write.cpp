@@ -1,0 +1,289 @@
+// dfx_parquet_write.cpp -- the executor of PhysicalPlan::Write { plan, filename, kind } (src/execution/physicalplan.rs:24-29) with
+// kind = Parquet (FileType::Parquet, dfparser.rs:31-36), which the reference declares and never runs (deviation D13; the twin of
+// dfx_csv_write.cpp, D11).
+//
+// A sink: it pulls its input to the end.  The schema is judged before a device is asked for.  The row sequence is cut by the shared
+// geometry (dfx_parquet_enc.hpp): row groups of exactly row_group_rows rows, pieces (the rows of one batch inside one group), pages of
+// page_rows rows.  Every piece is encoded in launch chains of at most pqw::launch_rows rows (dfx_k_parquet_write.hip): measure, scan,
+// the read-back of the page table, encode, the copy of the bodies into a pinned buffer -- the two host synchronisations of a launch.
+// A column chunk is contiguous in the file, so the pinned buffers of the open row group are held until it closes: at most one row
+// group's encoded bytes.  At the close every column's pages go to the file as [header][body], straight from the pinned buffers; the
+// host writes headers and the footer (dfx_parquet_thrift_write.hpp) and touches no value.  The bytes go to `filename` +
+// ".dfx-partial" and are renamed at the end.
+#include <errno.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "dfx_parquet_write.hpp"
+#include "dfx_relation.hpp"
+
+namespace dfx {
+
+namespace {
+
+using namespace pqw;
+
+struct PqwOptions {
+  int64_t row_group_rows = kDefaultRowGroupRows;
+  int64_t page_rows = kDefaultPageRows;
+};
+
+Status parse_options(const dfx_option* options, int32_t n_options, PqwOptions* o) {
+  for (int32_t i = 0; i < n_options; ++i) {
+    const char* key = options && options[i].key ? options[i].key : "(null)";
+    const int64_t v = options ? options[i].value : 0;
+    if (!strcmp(key, "row_group_rows")) {
+      if (!row_group_rows_ok(v)) return Status::Err(DFX_GENERAL, strfmt("row_group_rows = %lld: at least 1", (long long)v));
+      o->row_group_rows = v;
+    } else if (!strcmp(key, "page_rows")) {
+      if (!page_rows_ok(v)) return Status::Err(DFX_GENERAL, strfmt("page_rows = %lld: a multiple of 64 from 64 to 2^30", (long long)v));
+      o->page_rows = v;
+    } else {
+      return Status::Err(DFX_GENERAL, std::string("unknown option ") + key);
+    }
+  }
+  return Status::OK();
+}
+
+Status judge_schema(const SchemaInfo& sc) {
+  if (sc.fields.empty()) return Status::Err(DFX_GENERAL, "Parquet writer needs a schema with at least one column");
+  for (const Field& f : sc.fields)
+    if (!dtype_ok(f.dtype)) return Status::Err(DFX_NOT_IMPLEMENTED, strfmt("Parquet writer: column '%s' of type %s", f.name.c_str(), dtype_name(f.dtype)));
+  return Status::OK();
+}
+
+class ParquetSink {
+ public:
+  ParquetSink(std::unique_ptr<Relation> in, std::string filename, const PqwOptions& opt)
+      : in_(std::move(in)), final_(std::move(filename)), tmp_(final_ + ".dfx-partial"), opt_(opt), writer_(specs(in_->schema()), &ParquetSink::put, this) {}
+  ~ParquetSink() {
+    if (fp_) fclose(fp_);
+    if (fp_ || created_) remove(tmp_.c_str());
+  }
+  Status run(int64_t* rows, int64_t* bytes);
+
+ private:
+  struct HeldPage {
+    int64_t num_values, non_null;
+    const uint8_t* body;  // in one of held_buffers_
+    size_t bytes;
+  };
+  static std::vector<ColumnSpec> specs(const SchemaInfo& sc) {
+    std::vector<ColumnSpec> out;
+    for (const Field& f : sc.fields) {
+      ColumnSpec c;
+      c.name = f.name;
+      c.dtype = f.dtype;
+      c.nullable = f.nullable;
+      out.push_back(c);
+    }
+    return out;
+  }
+  static bool put(void* self, const void* p, size_t n) {
+    ParquetSink* s = (ParquetSink*)self;
+    if (fwrite(p, 1, n, s->fp_) == n) return true;
+    s->io_ = Status::Err(DFX_IO_ERROR, strfmt("write to %s failed: %s", s->tmp_.c_str(), strerror(errno)));
+    return false;
+  }
+  Status io_error() const { return io_.ok() ? Status::Err(DFX_IO_ERROR, "write to " + tmp_ + " failed") : io_; }
+  Status encode_rows(const DeviceBatch& b, int64_t r0, int64_t n);
+  Status encode_columns(const DeviceBatch& b, int c0, int nc, int64_t r0, int64_t n);
+  Status close_group();
+
+  std::unique_ptr<Relation> in_;
+  std::string final_, tmp_;
+  PqwOptions opt_;
+  FileWriter writer_;
+  FILE* fp_ = nullptr;
+  bool created_ = false;
+  Status io_;
+  int64_t group_rows_ = 0;                          // rows of the open row group
+  std::vector<std::vector<HeldPage>> held_;          // ... its encoded pages, column by column
+  std::vector<std::shared_ptr<void>> held_buffers_;  // ... the pinned buffers they lie in
+};
+
+// one launch chain over rows [r0, r0 + n) of columns [c0, c0 + nc) of the batch
+Status ParquetSink::encode_columns(const DeviceBatch& b, int c0, int nc, int64_t r0, int64_t n) {
+  hipStream_t s = ctx().stream;
+  const SchemaInfo& sc = in_->schema();
+  Status st;
+  DevPqwPlan plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.n_cols = nc;
+  plan.rows = n;
+  plan.page_rows = opt_.page_rows;
+  plan.n_tiles = tiles_of(n);
+  plan.n_pages = pages_of(n, opt_.page_rows);
+  bool any_boolean = false;
+  for (int k = 0; k < nc; ++k) {
+    const DeviceColumn& col = b.columns[(size_t)(c0 + k)];
+    DevPqwCol& d = plan.col[k];
+    if (col.absent || col.length < r0 + n || col.dtype != sc.fields[(size_t)(c0 + k)].dtype)
+      return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a column of the batch is absent, short or not of the schema's type");
+    d.dtype = (uint8_t)col.dtype;
+    d.optional = sc.fields[(size_t)(c0 + k)].nullable ? 1 : 0;
+    d.validity = (col.validity && col.null_count != 0) ? col.validity : nullptr;
+    d.bit_offset = col.bit_offset + r0;
+    if (col.dtype == DFX_UTF8) {
+      if (!col.offsets) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: Utf8 column without offsets");
+      d.offsets = col.offsets + r0;
+      d.data = col.data;
+    } else if (col.dtype == DFX_BOOLEAN) {
+      d.values = col.values;
+      any_boolean = true;
+    } else {
+      d.values = (const uint8_t*)col.values + (size_t)r0 * (size_t)dtype_width(col.dtype);
+    }
+  }
+  const int64_t n_tiles = plan.n_tiles * nc, n_pages = plan.n_pages * nc;
+  auto tiles = device_alloc(sizeof(PqwTile) * (size_t)n_tiles, &st);
+  if (!tiles) return st;
+  auto pages = device_alloc(sizeof(PqwPage) * (size_t)(n_pages + 1) + sizeof(uint64_t), &st);
+  if (!pages) return st;
+  auto table = pinned_alloc(sizeof(PqwPage) * (size_t)(n_pages + 1) + sizeof(uint64_t), &st);  // the page table, then the control word
+  if (!table) return st;
+  PqwPage* d_pages = (PqwPage*)pages.get();
+  uint64_t* ctrl = (uint64_t*)(d_pages + n_pages + 1);
+  DFX_HIP(hipMemsetAsync(ctrl, 0, sizeof(uint64_t), s));
+  DFX_HIP(launch_pqw_measure(plan, (PqwTile*)tiles.get(), s));
+  DFX_HIP(launch_pqw_scan(plan, (PqwTile*)tiles.get(), d_pages, s));
+  DFX_HIP(hipMemcpyAsync(table.get(), d_pages, sizeof(PqwPage) * (size_t)(n_pages + 1), hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));  // the page table: the one read-back of the launch
+  const PqwPage* pt = (const PqwPage*)table.get();
+  for (int k = 0; k < nc; ++k)
+    for (int64_t p = 0; p < plan.n_pages; ++p) {
+      const PqwPage& g = pt[(int64_t)k * plan.n_pages + p];
+      const int64_t page_n = std::min<int64_t>(opt_.page_rows, n - p * opt_.page_rows);
+      const Field& f = sc.fields[(size_t)(c0 + k)];
+      if (!f.nullable && (int64_t)g.non_null != page_n)
+        return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: column '%s' is not nullable (REQUIRED) and its batch holds %lld nulls in a page of %lld rows",
+                                                       f.name.c_str(), (long long)(page_n - (int64_t)g.non_null), (long long)page_n));
+      if (g.flags & PQW_PAGE_TOO_LARGE || !body_fits(g.level_bytes, g.val_bytes))
+        return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: a page of column '%s' takes %llu bytes; a page header holds sizes below 2^31 - 1 (smaller page_rows)",
+                                                       f.name.c_str(), (unsigned long long)(g.level_bytes + g.val_bytes)));
+    }
+  const uint64_t total = pt[n_pages].base;
+  auto out = device_alloc((size_t)total + 16, &st);
+  if (!out) return st;
+  auto host = pinned_alloc((size_t)total + 16, &st);
+  if (!host) return st;
+  if (any_boolean) DFX_HIP(hipMemsetAsync(out.get(), 0, (size_t)total + 16, s));  // Boolean pages are ORed into zeroes
+  DFX_HIP(launch_pqw_encode(plan, (const PqwTile*)tiles.get(), d_pages, (uint8_t*)out.get(), total, ctrl, s));
+  const uint64_t* hc = (const uint64_t*)((const PqwPage*)table.get() + n_pages + 1);
+  DFX_HIP(hipMemcpyAsync((void*)hc, ctrl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (total) DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));  // the bodies
+  if (*hc != 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: the measure and encode kernels disagree about a tile, or a tile would leave its page");
+  held_buffers_.push_back(host);
+  for (int k = 0; k < nc; ++k)
+    for (int64_t p = 0; p < plan.n_pages; ++p) {
+      const PqwPage& g = pt[(int64_t)k * plan.n_pages + p];
+      const uint64_t body = (uint64_t)g.level_bytes + g.val_bytes;
+      if (g.base > total || body > total - g.base) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a page lies outside its launch's buffer");
+      HeldPage h;
+      h.num_values = std::min<int64_t>(opt_.page_rows, n - p * opt_.page_rows);
+      h.non_null = (int64_t)g.non_null;
+      h.body = (const uint8_t*)host.get() + g.base;
+      h.bytes = (size_t)body;
+      held_[(size_t)(c0 + k)].push_back(h);
+      if (g.kind == LEVELS_MIXED) ++counters().parquet_write_bitpacked_level_pages;
+      else if (g.kind != LEVELS_NONE) ++counters().parquet_write_rle_level_pages;
+    }
+  return Status::OK();
+}
+
+Status ParquetSink::encode_rows(const DeviceBatch& b, int64_t r0, int64_t n) {
+  const int n_cols = (int)b.columns.size();
+  for (int c0 = 0; c0 < n_cols; c0 += kPqwMaxCols) DFX_RETURN_IF_ERROR(encode_columns(b, c0, std::min(kPqwMaxCols, n_cols - c0), r0, n));
+  return Status::OK();
+}
+
+// the open row group goes to the file: per column [header][body] of every page, offsets recorded by the writer
+Status ParquetSink::close_group() {
+  writer_.begin_row_group();
+  for (size_t c = 0; c < held_.size(); ++c) {
+    writer_.begin_chunk(c);
+    for (const HeldPage& h : held_[c])
+      if (!writer_.add_page(h.num_values, h.non_null, h.body, h.bytes)) return io_error();
+    held_[c].clear();
+  }
+  writer_.end_row_group(group_rows_);
+  held_buffers_.clear();
+  group_rows_ = 0;
+  return Status::OK();
+}
+
+Status ParquetSink::run(int64_t* rows, int64_t* bytes) {
+  const size_t n_cols = in_->schema().fields.size();
+  fp_ = fopen(tmp_.c_str(), "wb");
+  if (!fp_) return Status::Err(DFX_IO_ERROR, strfmt("cannot create %s: %s", tmp_.c_str(), strerror(errno)));
+  created_ = true;
+  if (!writer_.begin()) return io_error();
+  held_.assign(n_cols, std::vector<HeldPage>());
+  const int64_t per_launch = launch_rows(opt_.page_rows);
+  int64_t n_rows = 0;
+  for (;;) {
+    DeviceBatch b;
+    bool has = false;
+    DFX_RETURN_IF_ERROR(in_->next(&b, &has));
+    if (!has) break;
+    if (b.columns.size() != n_cols) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: batch and schema disagree");
+    for (int64_t r0 = 0; r0 < b.num_rows;) {
+      const int64_t piece = piece_rows(group_rows_, b.num_rows - r0, opt_.row_group_rows);
+      for (int64_t l0 = 0; l0 < piece; l0 += per_launch) DFX_RETURN_IF_ERROR(encode_rows(b, r0 + l0, std::min<int64_t>(per_launch, piece - l0)));
+      r0 += piece;
+      group_rows_ += piece;
+      if (group_rows_ == opt_.row_group_rows) DFX_RETURN_IF_ERROR(close_group());
+    }
+    n_rows += b.num_rows;
+  }
+  if (group_rows_ > 0) DFX_RETURN_IF_ERROR(close_group());
+  if (!writer_.finish()) return io_error();
+  FILE* fp = fp_;
+  fp_ = nullptr;
+  if (fclose(fp) != 0) return Status::Err(DFX_IO_ERROR, strfmt("closing %s failed: %s", tmp_.c_str(), strerror(errno)));
+  if (rename(tmp_.c_str(), final_.c_str()) != 0) return Status::Err(DFX_IO_ERROR, strfmt("cannot rename %s to %s: %s", tmp_.c_str(), final_.c_str(), strerror(errno)));
+  created_ = false;
+  counters().parquet_write_pages += writer_.pages();
+  counters().parquet_write_row_groups += writer_.row_groups();
+  counters().parquet_write_bytes += (long long)writer_.bytes();
+  if (rows) *rows = n_rows;
+  if (bytes) *bytes = (int64_t)writer_.bytes();
+  return Status::OK();
+}
+
+}  // namespace
+
+}  // namespace dfx
+
+using namespace dfx;
+
+extern "C" {
+
+int32_t dfx_parquet_write(struct ArrowArrayStream* input, const char* filename, const dfx_option* options, int32_t n_options,
+                          int64_t* rows_out, int64_t* bytes_out, char* err, size_t errlen) {
+  return c_abi_guard(err, errlen, [&]() -> int32_t {
+    if (!input || !filename) return to_c(Status::Err(DFX_GENERAL, "null argument"), err, errlen);
+    PqwOptions opt;
+    Status st = parse_options(options, n_options, &opt);
+    if (!st.ok()) return to_c(st, err, errlen);
+    std::unique_ptr<Relation> in;
+    st = adopt_input_stream(input, &in);  // (needs no device; a column type the library does not know is refused here, by name)
+    if (!st.ok()) return to_c(st, err, errlen);
+    st = judge_schema(in->schema());
+    if (!st.ok()) return to_c(st, err, errlen);
+    st = ensure_init();  // no device: nothing is created, there is no host encoding path
+    if (!st.ok()) return to_c(st, err, errlen);
+    ParquetSink sink(std::move(in), filename, opt);
+    st = sink.run(rows_out, bytes_out);
+    if (!st.ok()) {
+      (void)hipStreamSynchronize(ctx().stream);  // nothing of this call is in flight when its buffers go
+      return to_c(st, err, errlen);
+    }
+    return DFX_OK;
+  });
+}
+
+}  // extern "C"

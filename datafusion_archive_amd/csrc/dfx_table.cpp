@@ -522,6 +522,11 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "parquet_inflated_bytes")) return counters().parquet_inflated_bytes;
   if (!strcmp(name, "parquet_lz4_sequences")) return counters().parquet_lz4_sequences;
   if (!strcmp(name, "parquet_inflated_bytes_to_host")) return counters().parquet_inflated_bytes_to_host;
+  if (!strcmp(name, "parquet_write_pages")) return counters().parquet_write_pages;
+  if (!strcmp(name, "parquet_write_bytes")) return counters().parquet_write_bytes;
+  if (!strcmp(name, "parquet_write_rle_level_pages")) return counters().parquet_write_rle_level_pages;
+  if (!strcmp(name, "parquet_write_bitpacked_level_pages")) return counters().parquet_write_bitpacked_level_pages;
+  if (!strcmp(name, "parquet_write_row_groups")) return counters().parquet_write_row_groups;
   if (!strcmp(name, "xchg_calls")) return counters().xchg_calls;
   if (!strcmp(name, "xchg_local_us")) return counters().xchg_local_us;
   if (!strcmp(name, "xchg_wait_peers_us")) return counters().xchg_wait_peers_us;

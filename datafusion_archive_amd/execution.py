@@ -328,6 +328,20 @@ def write_csv(relation: Relation, filename: str, options: Optional[dict] = None)
     return rows.value, nbytes.value
 
 
+def write_parquet(relation: Relation, filename: str, options: Optional[dict] = None):
+    """The executor of PhysicalPlan::Write { plan, filename, kind: Parquet } (physicalplan.rs:24-29; the reference has none):
+    consumes `relation` to its end and writes it to `filename` as an uncompressed Parquet file of PLAIN V1 pages encoded on the
+    device (include/dfx.h: dfx_parquet_write has the format).  Returns (rows, bytes of the file).  `options`: "row_group_rows"
+    (default 2^20, >= 1) and "page_rows" (default 2^15, a multiple of 64); any other key is refused."""
+    err = _errbuf()
+    opts, n_opts, _keep = _options(options)
+    rows, nbytes = ctypes.c_int64(), ctypes.c_int64()
+    code = _ffi.lib().dfx_parquet_write(ctypes.byref(relation._take_stream()), os.fsencode(filename), opts, n_opts,
+                                        ctypes.byref(rows), ctypes.byref(nbytes), err, 1024)
+    _check(code, err)
+    return rows.value, nbytes.value
+
+
 class AggregateRelation(Relation):
     """aggregate::AggregateRelation::new(schema, input, group_expr, aggr_expr) (aggregate.rs:47-52)."""
 

@@ -386,6 +386,36 @@ int32_t dfx_csv_write(struct ArrowArrayStream* input, const char* filename, cons
                       int64_t* rows_out, int64_t* bytes_out, char* err, size_t errlen);
 
 /* ------------------------------------------------------------------------------------------
+ * Parquet writer.  The same sink with kind = Parquet: PhysicalPlan::Write { plan, filename, kind } (src/execution/physicalplan.rs:24-29)
+ * with FileType::Parquet beside CSV (dfparser.rs:31-36), which the reference declares and never runs.  It consumes `input` to its end
+ * (a stream of this library stays on the device, a foreign stream is uploaded like any operator input), encodes every page body on
+ * the device and writes `filename`.  rows_out / bytes_out (may be NULL): rows written, bytes of the file.  Deviation D13, parity
+ * unpinned.  The contract: what it writes, pyarrow reads back as the table that went in, bit for bit (names, types, field
+ * nullability, nulls, values by bit pattern: NaN payloads, -0.0 and null Utf8 slots included), and so does
+ * dfx_parquet_datasource_new.
+ *   format    PAR1; a flat schema, one leaf per input column, in order, with the input's names; a field the input schema flags
+ *             nullable is OPTIONAL, else REQUIRED.  Codec UNCOMPRESSED, data pages V1, encoding PLAIN, no dictionary pages, no page
+ *             CRC, no page index; chunk statistics carry null_count only; created_by names the library
+ *   types     Boolean -> BOOLEAN;  Int8 .. Int32, UInt8 .. UInt32 -> INT32 with Int(bits, signed) and the matching converted type,
+ *             values sign / zero extended to 4 bytes;  Int64 -> INT64;  UInt64 -> INT64 with Int(64, false);  Float32 -> FLOAT;
+ *             Float64 -> DOUBLE;  Utf8 -> BYTE_ARRAY annotated String / UTF8
+ *   levels    OPTIONAL columns: the V1 block {u32 length}{RLE / bit-packed hybrid, width 1} holding exactly ONE run per page: an RLE
+ *             run of 1 when every row of the page is valid, an RLE run of 0 when none is, else one bit-packed run of ceil(n / 8)
+ *             groups with zero padding bits -- by the page's own non-null count.  REQUIRED columns have no level block
+ *   geometry  the input's rows are cut into row groups of exactly "row_group_rows" rows (the last shorter; a batch that crosses a
+ *             boundary is split there); inside a group the rows of each batch are cut into pages of "page_rows" rows (the last
+ *             shorter): a page never holds rows of two batches.  Zero rows: a valid file with the schema and no row group
+ * `options`: "row_group_rows" (default 2^20, any value >= 1), "page_rows" (default 2^15; a multiple of 64, 64 .. 2^30); any other key
+ * or value is DFX_GENERAL.  Errors: a column type outside Boolean .. Utf8 is DFX_NOT_IMPLEMENTED naming the column and the type,
+ * before a file exists and before a device is asked for; no device is DFX_EXECUTION_ERROR (there is no host encoding path); a path
+ * that cannot be created or written is DFX_IO_ERROR; a REQUIRED field whose batch arrives with nulls is DFX_EXECUTION_ERROR naming
+ * the column; a page body of 2^31 - 1 bytes or more is DFX_EXECUTION_ERROR (the page header's sizes are i32).  The bytes go to
+ * `filename` + ".dfx-partial" and are renamed at the end: a failed call leaves nothing under either name.
+ * ---------------------------------------------------------------------------------------- */
+int32_t dfx_parquet_write(struct ArrowArrayStream* input, const char* filename, const dfx_option* options, int32_t n_options,
+                          int64_t* rows_out, int64_t* bytes_out, char* err, size_t errlen);
+
+/* ------------------------------------------------------------------------------------------
  * ORDER BY / LIMIT.  The operators behind LogicalPlan::Sort { expr: [Expr::Sort { expr, asc }], input, schema } and
  * LogicalPlan::Limit { limit, input, schema } (src/logicalplan.rs:313-338), which the reference's planner emits
  * (sqlplanner.rs:142-183) and its executor leaves at unimplemented!() (context.rs:113,194): there is no reference
@@ -558,7 +588,12 @@ int32_t dfx_set_option(const char* key, int64_t value);
  *   "parquet_pages"               pages walked by the host (dictionary pages included)
  *   "parquet_dict_pages", "parquet_plain_pages"   data pages whose values are dictionary indices / PLAIN values
  *   "parquet_rle_runs", "parquet_bitpacked_runs"  runs of the RLE / bit-packed hybrid the kernels walked (levels, indices, RLE Booleans)
- *   "parquet_host_walked_strings" length prefixes of PLAIN byte arrays the host chased (dictionary pages always, PLAIN data pages) */
+ *   "parquet_host_walked_strings" length prefixes of PLAIN byte arrays the host chased (dictionary pages always, PLAIN data pages)
+ * Parquet writer (they observe only; tests/test_gpu_parquet_write.py):
+ *   "parquet_write_pages", "parquet_write_row_groups"   data pages / row groups written
+ *   "parquet_write_bytes"         bytes of the files written
+ *   "parquet_write_rle_level_pages", "parquet_write_bitpacked_level_pages"   pages of OPTIONAL columns whose definition levels are
+ *                                 one RLE run (every row valid, or none) / one bit-packed run (valid and null rows) */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 
