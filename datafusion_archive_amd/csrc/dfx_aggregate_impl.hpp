@@ -337,6 +337,20 @@ struct AggregateRelation::Impl {
   bool both_shadows_bind(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t rows, int64_t row0);
   bool shadow_built_here = false;
   int64_t row8_launches = 0;  // (explain)
+  // The routed shadow (agg.routed_shadow; dfx_routed_shadow.hpp): pass 1's unfiltered output per window of the table, kept by the table.
+  // routed_pair: the resident (key, operand) columns this bound two-column batch reads, and the table row its first row is.
+  // routed_shadow_launch: a launch over exactly one window of a built shadow, of the shape that routes 8-byte rows today, is ONE
+  // kernel (Pass2Rows::narrow8_pred) -- *took says whether it was.  routed_shadow_maybe (drain, after the last batch): the build,
+  // by a query that bound the operand's shadow.  routed_split_rows: W if this batch's pair has a shadow (launches of whole windows).
+  bool routed_pair(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const void** keys, const void** values, int64_t* rows, int64_t* row) const;
+  Status routed_shadow_launch(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t row0, int64_t n, bool* took);
+  Status routed_shadow_maybe();
+  int64_t routed_split_rows(const DevProgram& prog, const DevColumns& cols) const;
+  const void* routed_keys = nullptr;  // the pair whose operand shadow a pass-1 launch of this query bound
+  const void* routed_values = nullptr;
+  int64_t routed_rows = 0;
+  int64_t routed_shadow_launches = 0;  // (explain)
+  uint32_t ws_scanners_of_build = 4;   // the build's split of scanner and router waves (the dense layout's)
   Status drain();
   Status emit_grouped(DeviceBatch* out, int64_t expected);
   std::shared_ptr<void> emit_total;  // pinned: the scan's group count

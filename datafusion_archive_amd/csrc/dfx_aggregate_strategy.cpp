@@ -205,7 +205,9 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b, int64_
   }
   {  // a scan that routes most of its rows: launches of at most partition_split_rows rows (regions sized for that many)
     // (selective scans: twice that -- 2^27-row launches measured best, 2^28-row ones 7 % slower)
-    const int64_t split = (dec.use_partition && o.partition_split_rows >= (1 << 20)) ? (((int64_t)o.partition_split_rows * (dec.dense_seen ? 1 : 2)) & ~(int64_t)63) : 0;
+    int64_t split = (dec.use_partition && o.partition_split_rows >= (1 << 20)) ? (((int64_t)o.partition_split_rows * (dec.dense_seen ? 1 : 2)) & ~(int64_t)63) : 0;
+    if (dec.use_partition && row0 == 0)  // (the table keeps a routed shadow of these columns: launches of whole windows, each one kernel)
+      if (const int64_t w = routed_split_rows(prog, cols)) split = w;
     launch_rows_hint = split;
     Status lst = Status::OK();
     if (split > 0 && n - row0 > split) {

@@ -467,6 +467,181 @@ bool AggregateRelation::Impl::both_shadows_bind(const DevProgram& prog, const De
   return vc >= 0 && memo->value_shadows.peek(cols.c[vc].values) != nullptr;
 }
 
+// ---- the routed shadow (dfx_routed_shadow.hpp) --------------------------------------------------------------------------------------
+bool AggregateRelation::Impl::routed_pair(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const void** keys, const void** values, int64_t* rows,
+                                          int64_t* row) const {
+  if (!input || !fp.valid || prog.n_cols != 2 || fp.keycol[0] >= 2) return false;
+  ScanMemo* memo = input->column_memo();
+  if (!memo) return false;
+  const int ks = fp.keycol[0];
+  int64_t krows = 0, vrows = 0, krow = 0, vrow = 0;
+  *keys = memo->key_shadows.column_of(cols.c[ks].values, &krows, &krow);
+  *values = memo->value_shadows.column_of(cols.c[1 - ks].values, &vrows, &vrow);
+  if (!*keys || !*values || krows != vrows || krow != vrow) return false;
+  *rows = krows;
+  *row = krow;
+  return true;
+}
+
+int64_t AggregateRelation::Impl::routed_split_rows(const DevProgram& prog, const DevColumns& cols) const {
+  if (opt().routed_shadow == 0 || kw != 1 || na() != 1) return 0;
+  const void *keys = nullptr, *values = nullptr;
+  int64_t rows = 0, row = 0;
+  if (!routed_pair(prog, fast_plan(), cols, &keys, &values, &rows, &row)) return 0;
+  return input->column_memo()->routed_shadows.window_rows_of(keys, values);
+}
+
+// the launch's DevPartition over a window's regions
+static DevPartition routed_partition(const RoutedGeometry& g, void* regions, void* counts) {
+  DevPartition pt = {};
+  pt.rows = (uint64_t*)regions, pt.counts = (uint32_t*)counts;
+  pt.part_stride = g.part_stride, pt.prod_stride = g.prod_stride, pt.win_stride = g.win_stride;
+  pt.n_parts = g.n_parts, pt.n_producers = g.n_producers, pt.cap_rows = g.cap_rows, pt.n_words = g.n_words, pt.part_shift = g.part_shift;
+  pt.mode = 2u, pt.block = 1024u, pt.flags = g.flags;
+  return pt;
+}
+
+// prog, fp, cols: the batch as the operator bound it (both_shadows_bind said yes: one SUM of the plain operand column, every
+// predicate term on it, no nulls, no calibration slice).  [row0, row0 + n) must be exactly one window, routed for this table's
+// geometry; a table that grew, another block count, a slice off the grid keep the two passes.
+Status AggregateRelation::Impl::routed_shadow_launch(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t row0, int64_t n, bool* took) {
+  *took = false;
+  if (opt().routed_shadow == 0 || calibrating || kw != 1 || na() != 1 || T.acc_kind[0] != ACC_ADD_F64 || T.val_xform[0] != VT_RAW) return Status::OK();
+  if (fp.np != 0 && fp.np != 2) return Status::OK();
+  const void *keys = nullptr, *values = nullptr;
+  int64_t col_rows = 0, at = 0;
+  if (!routed_pair(prog, fp, cols, &keys, &values, &col_rows, &at)) return Status::OK();
+  RoutedWindow w;
+  const uint32_t n_parts = (uint32_t)((T.mask + 1) / ((uint64_t)T.block_mask + 1));
+  if (!input->column_memo()->routed_shadows.bind(keys, values, at + row0, n, opt().routed_shadow, T.shift, T.block_mask + 1, n_parts, &w)) return Status::OK();
+  DevRowPred pred = {};
+  pred.np = (uint32_t)fp.np;
+  const int vc = 1 - fp.keycol[0];
+  for (int i = 0; i < fp.np; ++i) {
+    if (fp.term[i].col != vc || fp.term[i].dtype != T_F64) return Status::OK();  // (the signatures' terms: on the operand, as Float64)
+    pred.imm[i] = fp.term_imm[i], pred.m[i] = fp.term[i].m, pred.inv[i] = fp.term[i].inv;
+  }
+  DFX_RETURN_IF_ERROR(flush_pass2());  // (a pending window of routed rows first: the two paths may alternate, they aggregate into the same table)
+  hipStream_t s = ctx().stream;
+  DevPartition pt = routed_partition(w.g, w.regions.get(), w.counts.get());
+  // the kernel publishes the control block itself, as a window's closing pass 2 does (post_ctrl)
+  win.snap_armed = false;
+  if (opt().ctrl_snapshot == 1 && dec.calibrated) {
+    if (!ctl.host) DFX_RETURN_IF_ERROR(alloc_ctrl_host());
+    if (!win.snap_done) {
+      Status st;
+      win.snap_done = device_alloc(sizeof(uint32_t) * 16, &st);
+      if (!win.snap_done) return st;
+      DFX_HIP(hipMemsetAsync(win.snap_done.get(), 0, sizeof(uint32_t) * 16, s));
+    }
+    pt.snap_host = (uint32_t*)ctl.host.get() + (size_t)(ctl.batch_seq & 1) * CTRL_WORDS;
+    pt.snap_done = (uint32_t*)win.snap_done.get();
+    win.snap_armed = true;
+  }
+  DFX_HIP(launch_partition_scan(T, pt, spill, pred, 8.0 * (double)n, s));
+  win.last_p2_seq = ctl.batch_seq;
+  ++counters().agg_routed_shadow_launches;
+  ++routed_shadow_launches;
+  *took = true;
+  return Status::OK();
+}
+
+// After the query's last batch.  The build is the existing dense wave-specialised pass 1 over both column shadows (the SigKeySum
+// kernels of the key4 unit: SELECT k, SUM(v) GROUP BY k, every row routed), window by window into that window's own regions, in
+// launches of agg.partition_split_rows rows with PTF_RESUME; no pass 2.  It runs against a control block of its own and no spill
+// list: a row that finds no place in a region is counted there and nowhere else, and the count refuses the shadow for good.
+Status AggregateRelation::Impl::routed_shadow_maybe() {
+  const AggOptions& o = opt();
+  if (o.routed_shadow == 0 || !routed_keys || !input || !dec.use_partition || !dec.narrow || kw != 1 || na() != 1 || chunks.size() != 1) return Status::OK();
+  if (T.acc_kind[0] != ACC_ADD_F64 || T.val_xform[0] != VT_RAW || o.routed_row8 == 0) return Status::OK();
+  ScanMemo* memo = input->column_memo();
+  if (!memo || memo->routed_shadows.state_of(routed_keys, routed_values) > 0) return Status::OK();  // (built or refused already)
+  const uint32_t* key_words = memo->key_shadows.peek(routed_keys);
+  const uint32_t* value_words = memo->value_shadows.peek(routed_values);
+  if (!key_words || !value_words) return Status::OK();
+  hipStream_t s = ctx().stream;
+  Status ast;
+  std::shared_ptr<void> bctrl = device_alloc(sizeof(uint32_t) * CTRL_WORDS, &ast);
+  if (!bctrl) return Status::OK();  // (dropped: the next query asks again)
+  if (hipMemsetAsync(bctrl.get(), 0, sizeof(uint32_t) * CTRL_WORDS, s) != hipSuccess) {
+    (void)hipGetLastError();
+    return Status::OK();
+  }
+  DevTable Tb = T;
+  Tb.ctrl = (uint32_t*)bctrl.get();
+  Tb.stats = nullptr;
+  RoutedShadowDevice dev;
+  dev.free_bytes = []() -> size_t {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return free_b;
+  };
+  dev.alloc = [](size_t bytes) { return device_alloc_optional(bytes); };
+  dev.layout = [this](int64_t rows) -> RoutedWindowLayout {
+    RoutedLayoutQuery q = layout_query(rows, false, true);
+    q.has_pred = false, q.unfused_now = false, q.dense_seen = true, q.mostly_seen = true, q.skew_seen = false;  // every row is routed
+    const RoutedLayout L = choose_routed_layout(q);
+    RoutedWindowLayout l;
+    if (L.kind != RoutedLayoutKind::ring16 || !(L.PT.flags & PTF_ROW8) || !partition_launchable(L.PT)) return l;
+    RoutedGeometry& g = l.g;
+    g.n_parts = L.PT.n_parts, g.n_producers = L.PT.n_producers, g.cap_rows = L.PT.cap_rows, g.n_words = L.PT.n_words, g.part_shift = L.PT.part_shift;
+    g.flags = L.PT.flags, g.part_stride = L.PT.part_stride, g.prod_stride = L.PT.prod_stride, g.win_stride = L.PT.win_stride;
+    g.shift = T.shift, g.block_slots = T.block_mask + 1;
+    l.region_bytes = L.row_bytes, l.count_bytes = L.cnt_bytes;
+    ws_scanners_of_build = L.PT.ws_scanners;
+    return l;
+  };
+  dev.route = [&](int64_t row0, int64_t rows, const RoutedGeometry& g, void* regions, void* counts) -> bool {
+    DevProgram P = {};
+    P.n_cols = 2, P.col_dtype[0] = T_U32, P.col_dtype[1] = T_F32;
+    DevFastPlan F = {};
+    F.valid = 1, F.np = 0, F.keycol[0] = 0;
+    F.arg[0].nf = 1, F.arg[0].f[0].kind = FF_COL, F.arg[0].f[0].col = 1;
+    DevAggPlan plan = {};
+    plan.pred = kNoOperand;
+    const int64_t split = o.partition_split_rows >= (1 << 20) ? ((int64_t)o.partition_split_rows & ~(int64_t)63) : rows;
+    for (int64_t at = 0; at < rows; at += split) {
+      const int64_t n = std::min(split, rows - at);
+      DevColumns C = {};
+      C.c[0].values = key_words + row0 + at;
+      C.c[1].values = value_words + row0 + at;
+      DevPartition pt = routed_partition(g, regions, counts);
+      pt.ws_scanners = ws_scanners_of_build;
+      pt.flags |= PTF_KEY4 | PTF_VAL4 | (at > 0 ? PTF_RESUME : 0u);
+      if (launch_partition(P, F, C, plan, Tb, pt, no_spill_rows(), n, 8.0 * (double)n, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+    }
+    return true;
+  };
+  dev.finish = [&](uint64_t* spilled, uint32_t* error) -> bool {
+    uint32_t hc[CTRL_WORDS];
+    bool ok = hipMemcpyAsync(hc, bctrl.get(), sizeof(hc), hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = ok && hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      return false;
+    }
+    *spilled = ((uint64_t)hc[CTRL_SPILL_HI] << 32) | hc[CTRL_SPILL_LO];
+    *error = hc[CTRL_ERROR];
+    return true;
+  };
+  int64_t w_rows = (int64_t)o.routed_shadow_window_rows & ~(int64_t)63;
+  if (w_rows < 64) w_rows = kRoutedWindowRows;
+  bool built_now = false;
+  {
+    ScopedUs t_build(&counters().agg_routed_shadow_build_us);
+    built_now = memo->routed_shadows.build(routed_keys, routed_values, routed_rows, o.routed_shadow, true, w_rows, shadow_query_bytes(), dev);
+    (void)hipStreamSynchronize(s);  // (a dropped build's launches have passed before its buffers go)
+  }
+  if (built_now) ++counters().agg_routed_shadow_builds;
+  return Status::OK();
+}
+
 Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgram& prog_in, const DevColumns& cols_in,
                                             int64_t row0, int64_t n) {
   hipStream_t s = ctx().stream;
@@ -488,6 +663,11 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
     // the row form is the layout's: ask first whether this launch will bind both shadows (8-byte rows), then lay out.  A launch
     // that will not closes a pending window of 8-byte rows here (the form differs: flush_pass2, regions laid out again)
     const bool both = both_shadows_bind(prog_in, fast_plan(), cols_in, layout_rows, row0);
+    if (both) {  // exactly one window of the table's routed shadow: one kernel, no routing
+      bool took = false;
+      DFX_RETURN_IF_ERROR(routed_shadow_launch(prog_in, fast_plan(), cols_in, row0, n, &took));
+      if (took) return Status::OK();
+    }
     Status pst = ensure_partition(layout_rows, prog.has_nulls != 0, both);
     if (!pst.ok() && pst.code == DFX_NOT_IMPLEMENTED) partition_now = false;  // global-atomic path instead
     else if (!pst.ok()) return pst;
@@ -517,6 +697,10 @@ Status AggregateRelation::Impl::launch_rows(const DeviceBatch& b, const DevProgr
         bytes -= 4.0 * (double)n;
         ++counters().agg_value_shadow_launches;
         ++value_shadow_launches;
+        if (!routed_keys) {  // (the pair a routed shadow would be of: routed_shadow_maybe, after the last batch)
+          int64_t at = 0;
+          if (!routed_pair(prog_in, fpp, cols_in, &routed_keys, &routed_values, &routed_rows, &at)) routed_keys = nullptr;
+        }
       }
     }
     if (PT.flags & PTF_ROW8) {

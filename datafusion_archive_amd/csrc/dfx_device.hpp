@@ -295,6 +295,15 @@ struct DevPartition {
   uint32_t* snap_host; // [CTRL_WORDS], host memory (hipHostMalloc)
   uint32_t* snap_done; // device word: workgroups of this launch that have finished (reset by the last one)
 };
+// The predicate of a scan over a routed shadow (Pass2Rows::narrow8_pred, dfx_k_pass2.hip): none, or two terms on the operand, each
+// `operand <op> literal` compared as Float64 -- DevFastPlan's terms of the two signatures that bind the operand's Float32 shadow.
+struct DevRowPred {
+  uint64_t imm[2];  // the literals' Float64 bits
+  uint32_t m[2];    // three-way masks: 1 less, 2 equal, 4 greater
+  uint32_t inv[2];  // 1: NotEq
+  uint32_t np;      // 0 or 2
+  uint32_t pad;
+};
 enum : uint32_t {
   PTF_RESUME = 1u,        // pass 1 appends to the regions as `counts` left them (pass 2 of earlier batches is still pending)
   PTF_STREAM_PASS2 = 2u,  // pass 2: region-streaming kernel (one aggregate, 16-byte rows)

@@ -18,6 +18,7 @@
 #include "../../include/dfx.h"
 #include "dfx_device.hpp"
 #include "dfx_key_shadow.hpp"
+#include "dfx_routed_shadow.hpp"
 #include "dfx_value_shadow.hpp"
 #include "dfx_utf8_match.hpp"
 
@@ -167,6 +168,9 @@ struct Counters {
   long long agg_value_shadow_builds = 0;    // Float32 shadows of resident Float64 operand columns built (once per table and column)
   long long agg_value_shadow_launches = 0;  // pass-1 launches that read the operand from its shadow (PTF_VAL4: 8 bytes per row)
   long long agg_row8_launches = 0;          // ... that routed 8-byte rows {image, Float32 bits} (PTF_ROW8: every launch of the window bound both shadows)
+  long long agg_routed_shadow_builds = 0;    // routed shadows of resident (key, operand) column pairs built (dfx_routed_shadow.hpp: once per table and pair)
+  long long agg_routed_shadow_launches = 0;  // launches that scanned one window of a routed shadow (Pass2Rows::narrow8_pred: one kernel per window, no pass 1)
+  long long agg_routed_shadow_build_us = 0;  // ... wall time of the build attempts (a dense pass 1 per window + the read-back of its control block)
   long long agg_value_shadow_build_us = 0;  // ... wall time of the build attempts (kernel + the read-back of the not-exact word)
   long long agg_shared_operand_launches = 0;  // pass-1 launches that routed {image, shared raw operand} rows (PTF_SHARED)
   // COUNT(DISTINCT) (dfx_distinct.cpp)
@@ -293,6 +297,7 @@ struct Relation {
 struct ScanMemo {  // shared by every scan of a resident table (a `mutable` member of a const TableData): guarded
   mutable std::mutex mu;
   ValueShadows value_shadows;  // the Float32 copies of its null-free Float64 columns that are Float32-exact (dfx_value_shadow.hpp; its own lock)
+  RoutedShadows routed_shadows;  // pass 1's unfiltered output per (key column, operand column) pair, in windows of 2^27 rows (dfx_routed_shadow.hpp; its own lock)
   KeyShadows key_shadows;  // the Int32 copies of the table's null-free Int64 columns (dfx_key_shadow.hpp; its own lock)
   std::vector<std::pair<uint64_t, uint64_t>> calibrated_groups;  // (program fingerprint, groups in the first 2^18 rows)
   bool lookup(uint64_t fp, uint64_t* groups) const {

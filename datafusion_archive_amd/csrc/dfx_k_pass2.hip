@@ -1,6 +1,7 @@
 // dfx_k_pass2.hip -- pass 2 of the partitioned GROUP BY (the strategy: dfx_k_partition_inl.hpp): the flat-index kernel
 // k_partition_agg, the streaming kernel k_partition_agg_lean with its row forms, and launch_partition_agg.  Which form a launch
-// takes, with how much LDS and in how many launches, is choose_pass2 (dfx_pass2_forms.hpp, tested on the CPU).  build.py's guard
+// takes, with how much LDS and in how many launches, is choose_pass2 (dfx_pass2_forms.hpp, tested on the CPU).  The same kernel
+// scans a window of a table's routed shadow and evaluates the predicate itself (launch_partition_scan, choose_pass2_scan).  build.py's guard
 // of the hand-scheduled row registers compiles this unit a second time, to assembly.
 #include "dfx_k_partition_ws_inl.hpp"
 #include "dfx_pass2_forms.hpp"
@@ -376,17 +377,39 @@ DEV void p2_match2_narrow(const uint4& a, uint32_t img0, const uint4& b, uint32_
   i1 = x1;
 }
 
+// Pass2Rows::narrow8_pred (SCAN != kP2ScanNone): the regions are a window of a table's ROUTED SHADOW (dfx_routed_shadow.hpp) -- every
+// row of 2^27 consecutive table rows, routed once by a dense pass 1, read-only here -- and the query's predicate is evaluated in THIS
+// kernel: per trip the operand is widened (shadow_widen) and compared as Float64 with the query's literals, exactly the comparison
+// the Val4 scan policies make, and the passing rows are compacted (ballot + mbcnt) into a per-wave LDS ring of kP2StageRows rows.
+// Whenever the ring holds 128 rows, two full batches of it take the path below (decode, look2, apply, park); the remainder when
+// the wave's regions end.  SCAN: kP2ScanRuntime the operators are read from `pred`; kP2ScanAll no predicate; else the two terms'
+// three-way masks as compile-time constants (m0 | m1 << 3, as pass 1's FORM).
+template <int M>
+DEV bool p2_cmp_ct(double a, double b) {
+  if constexpr (M == 1) return a < b;
+  else if constexpr (M == 2) return a == b;
+  else if constexpr (M == 3) return a <= b;
+  else if constexpr (M == 4) return a > b;
+  else if constexpr (M == 5) return a < b || a > b;
+  else return a >= b;
+}
+DEV uint64_t p2_cmp_rt(double a, double b, uint32_t m, uint32_t inv) {  // (cmp_mask_by<double> ^ inv: the scan policies' run-time term)
+  const uint64_t lt = __ballot(a < b), eq = __ballot(a == b), gt = __ballot(a > b);
+  return (((m & 1u) ? lt : 0ull) | ((m & 2u) ? eq : 0ull) | ((m & 4u) ? gt : 0ull)) ^ (inv ? ~0ull : 0ull);
+}
+
 // ROWS: the row form (above).  KIND: the accumulator kind (ACC_*).  SHARED_OPERAND (PTF_SHARED; KIND is not read): T.na
 // (2..kSharedMaxAggs) aggregates of ONE operand -- the row carries the raw operand, every aggregate applies its own transform
 // and atomic to it (kinds and transforms are wave-uniform kernel arguments).
-template <typename ROWS, int KIND, bool SHARED_OPERAND = false>
+template <typename ROWS, int KIND, bool SHARED_OPERAND = false, int SCAN = kP2ScanNone>
 __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs))) void k_partition_agg_lean(const DevTable T, const DevPartition PT,
-                                                                                                             const DevRows spill) {
+                                                                                                             const DevRows spill, const DevRowPred pred) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
   static_assert(!SHARED_OPERAND || ROWS::kTags, "shared-operand rows are narrow rows");
   static_assert(ROWS::kTags ? (ROWS::kRowBytes == 12u || (ROWS::kRowBytes == 8u && !ROWS::kOperandFirst && !ROWS::kPlaneXform && !SHARED_OPERAND))
                             : (ROWS::kRowBytes == 16u && !ROWS::kOperandFirst && !ROWS::kPlaneXform),
                 "the six row forms");
+  static_assert(SCAN == kP2ScanNone || (ROWS::kRowBytes == 8u && KIND == ACC_ADD_F64), "the scan over a routed shadow reads 8-byte rows and adds");
   const uint32_t NA = SHARED_OPERAND ? (uint32_t)T.na : 1u;
   const uint32_t S = T.block_mask + 1;
   // PTF_PAIR (two aggregates of different operands, 20-byte routed rows): this launch aggregates operand / accumulator plane
@@ -637,6 +660,46 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
     park(q0);
     park(q1);
   };
+  // the scan's stage: a ring of kP2StageRows rows {image, Float32 bits} per wave, behind the parked-row queues
+  uint32_t* const stage = (uint32_t*)(ltags + S) + (size_t)kP2Waves * kRQ * kRW + (size_t)wave * (uint32_t)kP2StageRows * 2u;
+  uint32_t st_head = 0, st_n = 0;  // (wave-uniform)
+  uint64_t passed = 0;
+  auto stage_at = [&](uint32_t i) -> uint32_t* {  // row i behind the ring's head
+    uint32_t at = st_head + i;
+    at = at >= (uint32_t)kP2StageRows ? at - (uint32_t)kP2StageRows : at;
+    return stage + at * 2u;
+  };
+  auto drain2 = [&](uint32_t tk0, uint32_t tk1) __attribute__((always_inline)) {  // the ring's first rows as two batches (lanes past tk read rows nobody uses)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const uint2 a = *(const uint2*)stage_at((uint32_t)lane);
+    const uint2 b = *(const uint2*)stage_at(64u + (uint32_t)lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const uint32_t took = tk0 + tk1;
+    st_head += took;
+    st_head = st_head >= (uint32_t)kP2StageRows ? st_head - (uint32_t)kP2StageRows : st_head;
+    st_n -= took;
+    const Row4 r0 = {a.x, a.y, 0u, 0u}, r1 = {b.x, b.y, 0u, 0u};
+    process2(r0, tk0, r1, tk1);
+  };
+  auto scan1 = [&](const Row4& r, uint32_t tk) __attribute__((always_inline)) {
+    uint64_t pm = __ballot((uint32_t)lane < tk && r.x != kTagEmpty);
+    if constexpr (SCAN == kP2ScanRuntime) {
+      const double x = as_f64(shadow_widen(r.y));
+      if (pred.np > 0u) pm &= p2_cmp_rt(x, as_f64(pred.imm[0]), pred.m[0], pred.inv[0]);
+      if (pred.np > 1u) pm &= p2_cmp_rt(x, as_f64(pred.imm[1]), pred.m[1], pred.inv[1]);
+    } else if constexpr (SCAN != kP2ScanAll) {
+      const double x = as_f64(shadow_widen(r.y));
+      pm &= __ballot(p2_cmp_ct<(SCAN & 7)>(x, as_f64(pred.imm[0])));
+      pm &= __ballot(p2_cmp_ct<((SCAN >> 3) & 7)>(x, as_f64(pred.imm[1])));
+    }
+    if (pm != 0) {
+      if (lane_of_mask(pm)) *(uint2*)stage_at(st_n + mbcnt64(pm)) = make_uint2(r.x, r.y);
+      const uint32_t c = (uint32_t)__popcll(pm);
+      st_n += c;
+      passed += c;
+      if (st_n >= 128u) drain2(64u, 64u);
+    }
+  };
 #define DFX_P2_PAIR(D0, D1)                                                                                       \
   if (more) {                                                                                                     \
     const uint32_t tk0 = take[D0], tk1 = take[D1];                                                                \
@@ -652,11 +715,51 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
       if (tk1 == 0) more = false;                                                                                 \
     }                                                                                                             \
   }
-  while (more) {
-    DFX_P2_PAIR(0, 1) DFX_P2_PAIR(2, 3) DFX_P2_PAIR(4, 5) DFX_P2_PAIR(6, 7)
+  if constexpr (SCAN == kP2ScanNone) {
+    while (more) {
+      DFX_P2_PAIR(0, 1) DFX_P2_PAIR(2, 3) DFX_P2_PAIR(4, 5) DFX_P2_PAIR(6, 7)
+    }
+  } else {
+    // The scan: the four slot pairs are the cases of ONE loop body (a scalar switch per pair of trips), so the stage, and behind it
+    // process2 with its parked-row path, exist once per trip of the pair and not once per slot: unrolled over the eight slots the
+    // kernel was eight copies of all of it.
+    uint32_t phase = 0;
+    while (more) {
+      Row4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
+      uint32_t tk0 = 0, tk1 = 0;
+#define DFX_P2_TAKE2(D0, D1)                        \
+  {                                                 \
+    tk0 = take[D0], tk1 = take[D1];                 \
+    if (tk0 != 0) {                                 \
+      p2_take<D0, ROWS::kRowBytes, kPF - 1>(r0);    \
+      p2_take<D1, ROWS::kRowBytes, kPF - 2>(r1);    \
+      DFX_P2_FETCH(D0)                              \
+      DFX_P2_FETCH(D1)                              \
+    }                                               \
+  }
+      switch (phase) {
+        case 0: DFX_P2_TAKE2(0, 1) break;
+        case 1: DFX_P2_TAKE2(2, 3) break;
+        case 2: DFX_P2_TAKE2(4, 5) break;
+        default: DFX_P2_TAKE2(6, 7) break;
+      }
+#undef DFX_P2_TAKE2
+      phase = (phase + 1u) & 3u;
+      if (tk0 == 0) {
+        more = false;
+      } else {
+        scan1(r0, tk0);
+        scan1(r1, tk1);
+        if (tk1 == 0) more = false;
+      }
+    }
   }
 #undef DFX_P2_PAIR
 #undef DFX_P2_FETCH
+  if constexpr (SCAN != kP2ScanNone) {
+    if (st_n != 0) drain2(st_n < 64u ? st_n : 64u, st_n > 64u ? st_n - 64u : 0u);  // the ring's last rows (fewer than 128)
+    if (lane == 0) stat_add(T, STAT_PASSED, passed);                              // (the scanners of pass 1 count them otherwise)
+  }
   if (rqn != 0) {  // the wave's last parked rows (at most kRQ - 64 <= 64)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     retry((uint32_t)lane < rqn, (uint32_t)lane);
@@ -683,13 +786,14 @@ __global__ __launch_bounds__(kABlock) __attribute__((amdgpu_num_vgpr(kP2Vgprs)))
   for (int mm = 32; mm >= 1; mm >>= 1) new_keys += __shfl_xor(new_keys, mm, 64);
   if (lane == 0 && new_keys) atomicAdd(&T.ctrl[CTRL_OCCUPIED], new_keys);
   if (per_plane && plane != last_plane) return;  // (the last plane's launch reads the same regions: it is the one that ends the window)
-  if (p == 0 && threadIdx.x == 0) __hip_atomic_store(&T.ctrl[CTRL_MAX_FILL], 0u, RLX_AGENT);  // the regions are empty again
+  // (a routed shadow is read-only: its counts stand, its regions are never "empty again")
+  if (SCAN == kP2ScanNone && p == 0 && threadIdx.x == 0) __hip_atomic_store(&T.ctrl[CTRL_MAX_FILL], 0u, RLX_AGENT);  // the regions are empty again
   snapshot_ctrl_if_last(T, PT);
 }
 
 template <typename ROWS>
 static void launch_agg_lean(const DevTable& T, const DevPartition& PT, const DevRows& spill, size_t lds_bytes, hipStream_t s, int plane) {
-#define DFX_LEAN(K) hipLaunchKernelGGL((k_partition_agg_lean<ROWS, K>), dim3(PT.n_parts), dim3(kABlock), lds_bytes, s, T, PT, spill)
+#define DFX_LEAN(K) hipLaunchKernelGGL((k_partition_agg_lean<ROWS, K>), dim3(PT.n_parts), dim3(kABlock), lds_bytes, s, T, PT, spill, DevRowPred{})
   switch (T.acc_kind[plane]) {
     case ACC_ADD_F64: DFX_LEAN(ACC_ADD_F64); break;
     case ACC_ADD_F32: DFX_LEAN(ACC_ADD_F32); break;
@@ -723,7 +827,7 @@ hipError_t launch_partition_agg(const DevTable& T, const DevPartition& PT, const
     } else if (c.form == Pass2Form::flat_any) {
       hipLaunchKernelGGL(k_partition_agg<0>, grid, block, c.lds_bytes, s, T, Pa, spill);
     } else if (c.form == Pass2Form::shared_operand) {
-      hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow, ACC_ADD_F64, true>), grid, block, c.lds_bytes, s, T, Pa, spill);
+      hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow, ACC_ADD_F64, true>), grid, block, c.lds_bytes, s, T, Pa, spill, DevRowPred{});
     } else {
       switch (l.rows) {  // x the plane's accumulator kind
         case Pass2Rows::wide: launch_agg_lean<RowsWide>(T, Pa, spill, c.lds_bytes, s, a); break;
@@ -731,13 +835,36 @@ hipError_t launch_partition_agg(const DevTable& T, const DevPartition& PT, const
         case Pass2Rows::pair0: launch_agg_lean<RowsPair0>(T, Pa, spill, c.lds_bytes, s, a); break;
         case Pass2Rows::narrow_xf: launch_agg_lean<RowsNarrowXf>(T, Pa, spill, c.lds_bytes, s, a); break;
         case Pass2Rows::pair0_xf: launch_agg_lean<RowsPair0Xf>(T, Pa, spill, c.lds_bytes, s, a); break;
+        case Pass2Rows::narrow8_pred: return hipErrorInvalidValue;  // (launch_partition_scan's: choose_pass2 never names it)
         case Pass2Rows::narrow8:  // (only the two SUM signatures bind both shadows: one accumulator kind)
           if (T.acc_kind[a] != ACC_ADD_F64) return hipErrorInvalidValue;
-          hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow8, ACC_ADD_F64>), grid, block, c.lds_bytes, s, T, Pa, spill);
+          hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow8, ACC_ADD_F64>), grid, block, c.lds_bytes, s, T, Pa, spill, DevRowPred{});
           break;
       }
     }
   }
+  return hipGetLastError();
+}
+
+// One window of a routed shadow (dfx_routed_shadow.hpp) through the scan form: PT describes the window's regions and counts, pred
+// the query's predicate over the operand.  Which kernel, with how much LDS, is choose_pass2_scan (dfx_pass2_forms.hpp).
+hipError_t launch_partition_scan(const DevTable& T, const DevPartition& PT, const DevRows& spill, const DevRowPred& pred, double algo_bytes,
+                                 hipStream_t s) {
+  Scope sc(KID_PARTITION_AGG, s, algo_bytes);
+  const Pass2ScanChoice c = choose_pass2_scan(PT.flags, T.na, T.kw, T.acc_kind[0] == ACC_ADD_F64, T.block_mask + 1, PT.n_producers, kNarrowLine, pred.np, pred.m[0],
+                                              pred.inv[0], pred.m[1], pred.inv[1]);
+  if (c.rows != Pass2Rows::narrow8_pred) return hipErrorInvalidValue;
+  const dim3 grid(PT.n_parts), block(kABlock);
+#define DFX_SCAN(SCAN_) hipLaunchKernelGGL((k_partition_agg_lean<RowsNarrow8, ACC_ADD_F64, false, SCAN_>), grid, block, c.lds_bytes, s, T, PT, spill, pred)
+  switch (c.scan) {
+    case kP2ScanAll: DFX_SCAN(kP2ScanAll); break;
+    case 4 | (1 << 3): DFX_SCAN(4 | (1 << 3)); break;  // x >  a AND x <  b
+    case 6 | (1 << 3): DFX_SCAN(6 | (1 << 3)); break;  // x >= a AND x <  b
+    case 4 | (3 << 3): DFX_SCAN(4 | (3 << 3)); break;  // x >  a AND x <= b
+    case 6 | (3 << 3): DFX_SCAN(6 | (3 << 3)); break;  // x >= a AND x <= b
+    default: DFX_SCAN(kP2ScanRuntime); break;
+  }
+#undef DFX_SCAN
   return hipGetLastError();
 }
 

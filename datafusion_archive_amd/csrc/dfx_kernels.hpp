@@ -188,6 +188,8 @@ bool partition_planes_supported(const DevProgram& P, const DevFastPlan& fast, co
 bool partition_pair_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T);  // PTF_PAIR: this bound batch fits the pair kernels
 bool partition_key_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT);  // PTF_KEY4: a pass-1 kernel reads this batch's key from its Int32 shadow
 // PTF_VAL4: ... and the operand from its Float32 shadow.  P, PT: the launch with the key shadow already bound (key T_U32, PTF_KEY4)
+// one window of a routed shadow through pass 2's scan form (dfx_k_pass2.hip; dfx_routed_shadow.hpp)
+hipError_t launch_partition_scan(const DevTable& T, const DevPartition& PT, const DevRows& spill, const DevRowPred& pred, double algo_bytes, hipStream_t s);
 bool partition_value_shadow_supported(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevTable& T, const DevPartition& PT, int* operand_col);
 hipError_t launch_probe_wide_keys(const DevTable& T, hipStream_t s);
 hipError_t launch_partition(const DevProgram& P, const DevFastPlan& fast, const DevColumns& C, const DevAggPlan& plan,

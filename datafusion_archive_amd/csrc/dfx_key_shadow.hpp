@@ -98,6 +98,19 @@ class KeyShadows {
     }
     return nullptr;
   }
+  // the registered column that holds `values`: its base, *rows its length, *row the row `values` is (null: none)
+  const void* column_of(const void* values, int64_t* rows, int64_t* row) const {
+    if (!values) return nullptr;
+    std::lock_guard<std::mutex> lk(mu_);
+    for (const KeyShadow& c : cols_) {
+      const uint8_t* b = (const uint8_t*)c.base;
+      if ((const uint8_t*)values < b || (const uint8_t*)values >= b + (size_t)c.rows * 8) continue;
+      *rows = c.rows;
+      *row = (int64_t)(((const uint8_t*)values - b) / 8);
+      return c.base;
+    }
+    return nullptr;
+  }
   size_t bytes_held() const {
     std::lock_guard<std::mutex> lk(mu_);
     size_t b = 0;

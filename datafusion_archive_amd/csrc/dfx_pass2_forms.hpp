@@ -23,13 +23,16 @@ constexpr const char* kPass2FormName[] = {"flat_one", "flat_any", "stream_wide",
 // wide {key, operand}, the block holds keys; narrow {image, operand}, the block holds 32-bit tags; pair0 {operand lo, operand hi,
 // image}: operand 0 of a 20-byte pair row; *_xf: the operand is raw, the launch applies its plane's transform; narrow8 {image,
 // Float32 bits}: the decode widens the bits (shadow_widen), everything behind it is narrow's.
-enum class Pass2Rows : int { wide, narrow, pair0, narrow_xf, pair0_xf, narrow8 };
+// narrow8_pred: narrow8's rows read from a window of a table's routed shadow (dfx_routed_shadow.hpp), EVERY row of the window -- the
+// launch evaluates the query's predicate on the widened operand and stages the passing rows in LDS; choose_pass2_scan below.
+enum class Pass2Rows : int { wide, narrow, pair0, narrow_xf, pair0_xf, narrow8, narrow8_pred };
 
 constexpr int kP2Waves = 16;          // waves of a pass-2 workgroup (kABlock / 64)
 constexpr int kP2RetryRows = 128;     // per-wave queue of rows that missed their home group (narrow rows: 12 bytes each)
 constexpr int kP2RetryRowsWide = 96;  // ... 16-byte rows: 128 KB of block + 16 x 96 x 16 B = 152 KB of LDS
 constexpr int kSharedMaxAggs = 3;     // PTF_SHARED: 4096 slots x (4-byte tag + 3 accumulators) = 112 KB of LDS
 constexpr size_t kP2LdsLimit = 160 * 1024 - 256;
+constexpr int kP2StageRows = 192;     // narrow8_pred: per-wave ring of passing rows (8 bytes each): 127 left over + the 64 of one trip
 constexpr uint32_t kP2MaxProducers = 1024;  // (k_partition_agg scans the producer counts one per thread)
 
 struct Pass2Launch {
@@ -106,6 +109,40 @@ inline Pass2Choice choose_pass2(uint32_t flags, int na, int kw, uint32_t n_words
     take(Pass2Form::narrow, 1);
     c.launch[0].rows = Pass2Rows::narrow;
   }
+  return c;
+}
+
+// ---- the scan over a routed shadow (Pass2Rows::narrow8_pred) ---------------------------------------------------------------------
+// The comparison form of a launch, k_partition_agg_lean's SCAN: none (every other row form), the run-time form, no predicate, or the
+// two terms' three-way masks m0 | m1 << 3 for the four range forms pass 1 instantiates too (launch_partition_ws).
+constexpr int kP2ScanNone = -1, kP2ScanRuntime = 0, kP2ScanAll = 1;
+constexpr int pass2_scan_form(uint32_t np, uint32_t m0, uint32_t inv0, uint32_t m1, uint32_t inv1) {
+  if (np == 0) return kP2ScanAll;
+  if (np != 2 || inv0 || inv1) return kP2ScanRuntime;
+  if ((m0 == 4 || m0 == 6) && (m1 == 1 || m1 == 3)) return (int)(m0 | (m1 << 3));
+  return kP2ScanRuntime;
+}
+// LDS: narrow's block and parked-row queues, and sixteen stages
+constexpr size_t pass2_scan_lds_bytes(uint32_t slots) { return pass2_lds_bytes(Pass2Form::narrow, slots, 1, 0) + (size_t)kP2Waves * kP2StageRows * 8; }
+
+struct Pass2ScanChoice {
+  Pass2Rows rows = Pass2Rows::wide;  // narrow8_pred, or (refused) anything else
+  int scan = kP2ScanNone;
+  size_t lds_bytes = 0;
+};
+// flags: the window's layout flags; na, kw: T's; sum_f64: the one accumulator adds Float64; np ... inv1: the predicate's terms.
+// Refused: anything but one SUM over 8-byte rows in whole-line chunks, a predicate of one or three and more terms, a block that
+// does not fit.
+inline Pass2ScanChoice choose_pass2_scan(uint32_t flags, int na, int kw, bool sum_f64, uint32_t slots, uint32_t n_producers, bool narrow_line, uint32_t np,
+                                         uint32_t m0, uint32_t inv0, uint32_t m1, uint32_t inv1) {
+  Pass2ScanChoice c;
+  const uint32_t need = PTF_NARROW | PTF_CHUNK16 | PTF_ROW8;
+  if ((flags & need) != need || (flags & (PTF_SHARED | PTF_PAIR | PTF_PLANES | PTF_HOT)) || !narrow_line) return c;
+  if (na != 1 || kw != 1 || !sum_f64 || (np != 0 && np != 2) || n_producers == 0 || n_producers > kP2MaxProducers) return c;
+  if (slots < 64 || (slots & (slots - 1)) || pass2_scan_lds_bytes(slots) > kP2LdsLimit) return c;
+  c.rows = Pass2Rows::narrow8_pred;
+  c.scan = pass2_scan_form(np, m0, inv0, m1, inv1);
+  c.lds_bytes = pass2_scan_lds_bytes(slots);
   return c;
 }
 

@@ -85,6 +85,10 @@ struct AggOptions {
   int value_shadow = -1;       // the Float32 shadow of a resident table's null-free Float64 operand column whose every value is Float32-exact
                                // (dfx_value_shadow.hpp: with the key shadow pass 1 reads 8 bytes per row instead of 12; no bit of any result
                                // changes): -1 / 0 / 1 as agg.key_shadow
+  int routed_shadow = -1;      // the routed shadow of a resident table's (key, operand) column pair (dfx_routed_shadow.hpp): -1 built after the last batch
+                               // of a query that bound the operand's shadow, 0 never built nor read, 1 built by the first query that qualifies.
+                               // A launch over exactly one of its windows is one kernel that evaluates the predicate itself
+  int routed_shadow_window_rows = 1 << 27;  // rows per window (tests: 2^16 .. 2^18); a multiple of 64
   int routed_row8 = -1;        // 8-byte routed rows {hash image, Float32 bits} in the one-value wave-specialised layout when every launch of a
                                // window binds both shadows (PTF_ROW8: pass 1 appends 8 bytes per routed row instead of 12.8, pass 2 widens):
                                // -1 by that rule, 0 never

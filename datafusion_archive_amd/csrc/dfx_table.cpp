@@ -268,6 +268,8 @@ bool set_option_in(AggOptions& o, const char* key, int64_t value) {
   else if (!strcmp(key, "agg.key_shadow")) o.key_shadow = (int)value;
   else if (!strcmp(key, "agg.value_shadow")) o.value_shadow = (int)value;
   else if (!strcmp(key, "agg.routed_row8")) o.routed_row8 = (int)value;
+  else if (!strcmp(key, "agg.routed_shadow")) o.routed_shadow = (int)value;
+  else if (!strcmp(key, "agg.routed_shadow_window_rows")) o.routed_shadow_window_rows = (int)value;
   else if (!strcmp(key, "agg.narrow_chunk16")) o.narrow_chunk16 = (int)value;
   else if (!strcmp(key, "agg.shared_operand")) o.shared_operand = (int)value;
   else if (!strcmp(key, "agg.ctrl_snapshot")) o.ctrl_snapshot = (int)value;
@@ -490,6 +492,9 @@ int64_t dfx_counter_get(const char* name) {
   if (!strcmp(name, "agg_value_shadow_launches")) return counters().agg_value_shadow_launches;
   if (!strcmp(name, "agg_value_shadow_build_us")) return counters().agg_value_shadow_build_us;
   if (!strcmp(name, "agg_row8_launches")) return counters().agg_row8_launches;
+  if (!strcmp(name, "agg_routed_shadow_builds")) return counters().agg_routed_shadow_builds;
+  if (!strcmp(name, "agg_routed_shadow_launches")) return counters().agg_routed_shadow_launches;
+  if (!strcmp(name, "agg_routed_shadow_build_us")) return counters().agg_routed_shadow_build_us;
   if (!strcmp(name, "agg_pair_fallbacks")) return counters().agg_pair_fallbacks;
   if (!strcmp(name, "agg_growths")) return counters().agg_growths;
   if (!strcmp(name, "agg_shared_operand_launches")) return counters().agg_shared_operand_launches;

@@ -28,6 +28,7 @@ class ValueShadows {
     return rule_.acquire(values, option, first_ask, query_bytes, dev, built);
   }
   const uint32_t* peek(const void* values) const { return rule_.peek(values); }  // the words if the copy exists; no side effects
+  const void* column_of(const void* values, int64_t* rows, int64_t* row) const { return rule_.column_of(values, rows, row); }
   size_t bytes_held() const { return rule_.bytes_held(); }
   // (tests) -1 unknown, 0 nothing built, 1 built, 2 refused (not Float32-exact); *queries: askers so far
   int state_of(const void* values, int* queries = nullptr) const { return rule_.state_of(values, queries); }
