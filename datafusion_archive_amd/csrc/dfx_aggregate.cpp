@@ -524,10 +524,10 @@ void AggregateRelation::explain(std::string* out, int depth) const {
                      "aggregate (its own fused program and accumulator plane over the same keys: 12-byte routed rows, the one-aggregate "
                      "kernels; agg.split_aggregates)", m.na_total);
     if (m.phase == Impl::Phase::PerAggregate) text += strfmt("; ran one scan per aggregate (%d scans per batch: agg.split_aggregates)", (int)m.chunks.size());
-    if (m.key_shadow_launches > 0) text += strfmt("; %lld pass-1 launches read the key from its Int32 shadow (4 bytes of key per row instead of 8: agg.key_shadow)", (long long)m.key_shadow_launches);
-    if (m.value_shadow_launches > 0) text += strfmt("; %lld of them read the operand from its Float32 shadow as well (every value of the column is exactly its float: 8 bytes per row, agg.value_shadow)", (long long)m.value_shadow_launches);
-    if (m.row8_launches > 0) text += strfmt("; %lld of those routed 8-byte rows {hash image, Float32 bits} (row8: sixteen rows per 128-byte line, pass 2 widens the bits; agg.routed_row8)", (long long)m.row8_launches);
-    if (m.routed_shadow_launches > 0) text += strfmt("; %lld launches scanned a window of the table's routed shadow (narrow8_pred: one kernel per window reads the kept 8-byte rows and evaluates the predicate, no pass 1; agg.routed_shadow)", (long long)m.routed_shadow_launches);
+    if (m.shadows.key_shadow_launches > 0) text += strfmt("; %lld pass-1 launches read the key from its Int32 shadow (4 bytes of key per row instead of 8: agg.key_shadow)", (long long)m.shadows.key_shadow_launches);
+    if (m.shadows.value_shadow_launches > 0) text += strfmt("; %lld of them read the operand from its Float32 shadow as well (every value of the column is exactly its float: 8 bytes per row, agg.value_shadow)", (long long)m.shadows.value_shadow_launches);
+    if (m.shadows.row8_launches > 0) text += strfmt("; %lld of those routed 8-byte rows {hash image, Float32 bits} (row8: sixteen rows per 128-byte line, pass 2 widens the bits; agg.routed_row8)", (long long)m.shadows.row8_launches);
+    if (m.shadows.routed_shadow_launches > 0) text += strfmt("; %lld launches scanned a window of the table's routed shadow (narrow8_pred: one kernel per window reads the kept 8-byte rows and evaluates the predicate, no pass 1; agg.routed_shadow)", (long long)m.shadows.routed_shadow_launches);
     if (!m.dicts.empty()) text += strfmt(", %d Utf8 keys dictionary-encoded on the device", (int)m.dicts.size());
     if (m.built && m.kw > 0)  // after the input was drained: what actually ran
       text += strfmt("; ran %lld rows: %s, %llu of 2^%d table slots occupied", (long long)m.rows_seen,

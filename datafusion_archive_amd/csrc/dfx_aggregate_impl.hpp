@@ -2,7 +2,10 @@
 // (dfx_aggregate*.cpp include it, nothing else does; dfx_relation.hpp only forward-declares Impl).
 //   dfx_aggregate.cpp           set-up, chunks of accumulators, explain, next, drain
 //   dfx_aggregate_strategy.cpp  one batch through the strategy state machine (Phase, StrategyDecision)
-//   dfx_aggregate_table.cpp     table, spill list, routing regions (Pass2Window), launches, control-block checks (CtrlPipeline)
+//   dfx_aggregate_table.cpp     the table and its spill list: allocation, growth and replay
+//   dfx_aggregate_ctrl.cpp      control-block checks one batch behind the launches (CtrlPipeline)
+//   dfx_aggregate_shadow.cpp    the column shadows a launch binds, the routed shadow (ShadowBindings)
+//   dfx_aggregate_launch.cpp    routing regions (Pass2Window), the launches of one slice of rows
 //   dfx_aggregate_emit.cpp      the key column ahead of time (EarlyKeys), the result batch
 //   dfx_aggregate_partial.cpp   multi-GPU export / import
 // The Utf8 key dictionaries are Utf8Dict (dfx_utf8_dict.hpp), shared with the distinct-set aggregates.
@@ -14,6 +17,7 @@
 
 #include <algorithm>
 
+#include "dfx_agg_rules.hpp"
 #include "dfx_pass1_layout.hpp"
 #include "dfx_relation.hpp"
 #include "dfx_sigs.hpp"
@@ -21,11 +25,7 @@
 
 namespace dfx {
 
-inline int ceil_log2(uint64_t v) {
-  int l = 0;
-  while ((1ull << l) < v && l < 62) ++l;
-  return l;
-}
+inline uint64_t ctrl_spilled(const uint32_t* hc) { return ((uint64_t)hc[CTRL_SPILL_HI] << 32) | hc[CTRL_SPILL_LO]; }  // the spill cursor of a control block on the host
 
 inline DevRows no_spill_rows() {  // for kernels that must not spill (rehash, merges into a table sized for its rows)
   DevRows r;
@@ -105,6 +105,17 @@ struct CtrlPipeline {
   int64_t batch_seq = 0;
   uint64_t unconfirmed_rows = 0;               // rows of launched batches whose control block is not examined yet
   void forget() { pending[0] = pending[1] = false, unconfirmed_rows = 0; }  // a synchronous read of the block supersedes the snapshots
+};
+
+// What one query knows of the resident table's shadows (ScanMemo: dfx_key_shadow.hpp, dfx_value_shadow.hpp, dfx_routed_shadow.hpp).
+struct ShadowBindings {
+  bool key_shadow_asked = false, value_shadow_asked = false;  // the query's first question of each column shadow may build it
+  bool shadow_built_here = false;      // a query that builds a shadow itself keeps its 12-byte rows to the end (both_shadows_bind)
+  int64_t key_shadow_launches = 0, value_shadow_launches = 0, row8_launches = 0, routed_shadow_launches = 0;  // (explain)
+  // the (key, operand) pair whose operand shadow a pass-1 launch of this query bound: what routed_shadow_maybe builds the routed shadow of
+  const void *routed_keys = nullptr, *routed_values = nullptr;
+  int64_t routed_rows = 0;
+  uint32_t ws_scanners_of_build = 4;   // the build's split of scanner and router waves (the dense layout's)
 };
 
 struct AggregateRelation::Impl {
@@ -304,39 +315,43 @@ struct AggregateRelation::Impl {
   const AggOptions& opt() const { return options.get(); }
 
   Status setup(const SchemaInfo& input_schema);
-  Status alloc_table(int cap_log2, DevTable* T, std::vector<std::shared_ptr<void>>* owners, bool new_ctrl, uint64_t** full_accs_out);
-  void replace_table(const DevTable& Tn, uint64_t* accs_full_new, const std::vector<std::shared_ptr<void>>& owners, bool forget_snapshot);
-  Status ensure_spill(int64_t rows);
-  // both_shadows: every launch these regions are sized for binds both column shadows (launch_rows: both_shadows_bind)
-  Status ensure_partition(int64_t rows, bool nulls_now = false, bool both_shadows = false);
-  RoutedLayoutQuery layout_query(int64_t rows, bool nulls_now, bool both_shadows) const;
-  bool shared_operand() const;
-  Status flush_pass2();
   uint64_t program_fingerprint() const;
-  Status grow_and_replay(uint64_t occupied, uint64_t spilled, uint64_t replay_from = 0);
   Status consume_batch(const DeviceBatch& b);
   // decided != nullptr: return as soon as the strategy is decided; *decided = the rows of b that are done by then
   Status consume_batch_chunk(const DeviceBatch& b, int64_t* decided = nullptr);
-  Status launch_rows(const DeviceBatch& b, const DevProgram& prog, const DevColumns& cols, int64_t row0, int64_t n);
+  int widest_chunk() const {  // accumulators of the widest chunk: what a slot of the table, a row of the spill list holds at most
+    int widest = 0;
+    for (const Chunk& ch : chunks) widest = std::max(widest, ch.n);
+    return widest;
+  }
+  // ---- dfx_aggregate_table.cpp
+  Status alloc_table(int cap_log2, DevTable* T, std::vector<std::shared_ptr<void>>* owners, bool new_ctrl, uint64_t** full_accs_out);
+  Status ensure_spill(int64_t rows);
+  Status grow_and_replay(uint64_t occupied, uint64_t spilled, uint64_t replay_from = 0);
+  void replace_table(const DevTable& Tn, uint64_t* accs_full_new, const std::vector<std::shared_ptr<void>>& owners, bool forget_snapshot);
+  // ---- dfx_aggregate_ctrl.cpp
+  Status read_ctrl(uint32_t* host_ctrl);
+  Status alloc_ctrl_host();
+  Status post_ctrl(int64_t rows);
+  Status arm_snapshot(uint32_t** snap_to);
+  Status handle_ctrl(const uint32_t* hc, int64_t n);
+  Status examine_ctrl(int slot);
+  Status settle_ctrl();
+  Status finish_launched(int64_t rows, bool read_back = true);
+  // ---- dfx_aggregate_shadow.cpp
+  ShadowBindings shadows;
+  size_t shadow_query_bytes() const;  // the memory rule's "what this query holds"
   // The key column's Int32 shadow (agg.key_shadow; dfx_key_shadow.hpp): the 4-byte words of the key rows this bound batch starts at,
   // or null -- no resident table below, another shape, wide keys, nulls, the option, memory.  The query's first question may build it.
   const uint32_t* key_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt);
-  bool key_shadow_asked = false;
-  int64_t key_shadow_launches = 0;  // (explain)
   // ... and the operand column's Float32 shadow (agg.value_shadow; dfx_value_shadow.hpp), only beside a bound key shadow: prog, pt are
   // the launch's with the key already bound.  *operand_col: the slot it belongs in
   const uint32_t* value_shadow_words(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt, int* operand_col);
-  size_t shadow_query_bytes() const;  // the memory rule's "what this query holds"
-  bool value_shadow_asked = false;
-  int64_t value_shadow_launches = 0;  // (explain)
   // The routed row form (agg.routed_row8): would a launch of this bound batch bind BOTH shadows -- each eligible and already built?
-  // Asked before ensure_partition, without side effects: nothing is counted, nothing is built.  A query that builds a shadow
-  // itself keeps its 12-byte rows to the end (shadow_built_here).
+  // Asked before ensure_partition, without side effects: nothing is counted, nothing is built.
   int key_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const;    // -1: not this launch
   int value_shadow_column(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevPartition& pt) const;  // -1: not this launch
   bool both_shadows_bind(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t rows, int64_t row0);
-  bool shadow_built_here = false;
-  int64_t row8_launches = 0;  // (explain)
   // The routed shadow (agg.routed_shadow; dfx_routed_shadow.hpp): pass 1's unfiltered output per window of the table, kept by the table.
   // routed_pair: the resident (key, operand) columns this bound two-column batch reads, and the table row its first row is.
   // routed_shadow_launch: a launch over exactly one window of a built shadow, of the shape that routes 8-byte rows today, is ONE
@@ -346,11 +361,19 @@ struct AggregateRelation::Impl {
   Status routed_shadow_launch(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, int64_t row0, int64_t n, bool* took);
   Status routed_shadow_maybe();
   int64_t routed_split_rows(const DevProgram& prog, const DevColumns& cols) const;
-  const void* routed_keys = nullptr;  // the pair whose operand shadow a pass-1 launch of this query bound
-  const void* routed_values = nullptr;
-  int64_t routed_rows = 0;
-  int64_t routed_shadow_launches = 0;  // (explain)
-  uint32_t ws_scanners_of_build = 4;   // the build's split of scanner and router waves (the dense layout's)
+  // ---- dfx_aggregate_launch.cpp
+  bool shared_operand() const;
+  RoutedLayoutQuery layout_query(int64_t rows, bool nulls_now, bool both_shadows) const;
+  // both_shadows: every launch these regions are sized for binds both column shadows (launch_rows: both_shadows_bind)
+  Status ensure_partition(int64_t rows, bool nulls_now = false, bool both_shadows = false);
+  Status flush_pass2(uint32_t* snap_to = nullptr);  // snap_to: this pass 2 publishes the control block there (arm_snapshot)
+  Status launch_rows(const DeviceBatch& b, const DevProgram& prog, const DevColumns& cols, int64_t row0, int64_t n);
+  // launch_rows' steps (described where they are defined)
+  Status bind_shadows(const DevProgram& prog_in, const DevColumns& cols_in, const DevFastPlan& fp, int64_t row0, int64_t n, int64_t layout_rows,
+                      DevProgram* prog, DevColumns* cols, DevPartition* pt, double* bytes);
+  bool window_closes() const { return window_must_close(calibrating, win.pending, opt().partition_defer_batches, pair_scan(), win.fill_bound, win.worst, PT.cap_rows); }
+  Status launch_routed(const DevProgram& prog, const DevFastPlan& fp, const DevColumns& cols, const DevAggPlan& p, DevPartition pt, int64_t n, double bytes);
+  Status launch_table(const DevProgram& prog, const DevColumns& cols, DevAggPlan p, int64_t n, double bytes);
   Status drain();
   Status emit_grouped(DeviceBatch* out, int64_t expected);
   std::shared_ptr<void> emit_total;  // pinned: the scan's group count
@@ -420,13 +443,6 @@ struct AggregateRelation::Impl {
   uint64_t early_last_occupied = ~0ull;  // the group count of the previous snapshot
   Status early_keys_maybe();
   Status emit_ungrouped(DeviceBatch* out);
-  Status read_ctrl(uint32_t* host_ctrl);
-  Status post_ctrl(int64_t rows);
-  Status alloc_ctrl_host();
-  Status examine_ctrl(int slot);
-  Status settle_ctrl();
-  Status handle_ctrl(const uint32_t* hc, int64_t n);
-  Status finish_launched(int64_t rows, bool read_back = true);
   ~Impl() {
     if (ctl.pending[0] || ctl.pending[1]) (void)hipStreamSynchronize(ctx().aux);  // snapshots still in flight
     for (int i = 0; i < 2; ++i) {

@@ -130,8 +130,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b, int64_
   // itself, when its block is full)
   // (pair scan: a row whose key finds no slot in its block is spilled once per OPERAND -- by the last plane of each, dfx_k_pass2.hip --;
   // planes of a shared operand: once.  Their windows hold at most two batches, launch_rows)
-  const int64_t window_rows = dec.use_partition ? (pair_scan() ? (int64_t)std::min(2, std::max(1, opt().partition_defer_batches)) * (split_is_shared ? 1 : 2)
-                                                         : (int64_t)std::max(1, opt().partition_defer_batches)) * std::max(n, win.layout_rows) : 0;
+  const int64_t window_rows = spill_window_rows(dec.use_partition, pair_scan(), split_is_shared, opt().partition_defer_batches, n, win.layout_rows);
   if (may_spill) DFX_RETURN_IF_ERROR(ensure_spill(2 * n + window_rows + 65536));
   T.max_probe = may_spill ? 128 : (int)std::min<uint64_t>(T.mask + 1, 1u << 30);
   int64_t row0 = 0;
@@ -159,7 +158,7 @@ Status AggregateRelation::Impl::consume_batch_chunk(const DeviceBatch& b, int64_
     uint32_t hc[CTRL_WORDS];
     DFX_RETURN_IF_ERROR(read_ctrl(hc));
     if (hc[CTRL_ERROR]) return error_from_ctrl(hc[CTRL_ERROR]);
-    if ((((uint64_t)hc[CTRL_SPILL_HI] << 32) | hc[CTRL_SPILL_LO]) > 0 || hc[CTRL_SATURATED]) {
+    if (ctrl_spilled(hc) > 0 || hc[CTRL_SATURATED]) {
       // The slice did not fit the table (a table that starts very small: agg.capacity_log2): its spilled rows sit in the spill list
       // that the strategy decision below is about to REPLACE by a larger one.  Round 6, found by a test of the pair scan at 2^14
       // slots: nothing replayed them first -- the spill cursor went on counting them, the rebuild after the batch replayed whatever

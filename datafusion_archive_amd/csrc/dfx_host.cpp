@@ -333,6 +333,12 @@ Counters& counters() {
 std::shared_ptr<void> device_alloc(size_t bytes, Status* st) { return pool_alloc(dev_pool(), bytes, st); }
 std::shared_ptr<void> pinned_alloc(size_t bytes, Status* st) { return pool_alloc(pin_pool(), bytes, st); }
 std::shared_ptr<void> device_alloc_optional(size_t bytes) { return pool_alloc(dev_pool(), bytes, nullptr, false); }
+size_t device_free_bytes() {
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) return free_b;
+  (void)hipGetLastError();
+  return 0;
+}
 void pool_trim() {
   dev_pool().trim();
   pin_pool().trim();

@@ -216,6 +216,7 @@ std::shared_ptr<void> device_alloc(size_t bytes, Status* st);
 std::shared_ptr<void> pinned_alloc(size_t bytes, Status* st);
 // ... for work the query does not need (the key shadow): one attempt -- no cached block is released for it, no retry
 std::shared_ptr<void> device_alloc_optional(size_t bytes);
+size_t device_free_bytes();  // ... and what such an allocation can still have (0: the runtime would not say)
 void pool_trim();
 void pool_inject_oom(int n);  // test hook (dfx_set_option "pool.inject_oom"): the next n device allocations fail their first attempt for real
 

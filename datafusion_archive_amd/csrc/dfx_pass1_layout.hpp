@@ -1,5 +1,5 @@
 // dfx_pass1_layout.hpp -- pass 1 of the partitioned GROUP BY: its LDS arithmetic, THE list of routed layouts and which one a
-// table takes.  choose_routed_layout is everything AggregateRelation::Impl::ensure_partition (dfx_aggregate_table.cpp) decides
+// table takes.  choose_routed_layout is everything AggregateRelation::Impl::ensure_partition (dfx_aggregate_launch.cpp) decides
 // before it allocates: the flavour that routes the rows or a refusal, the row form, the region geometry, strides and capacities.
 // select_pass1 (dfx_k_partition.hip) and choose_pass2 (dfx_pass2_forms.hpp) take its DevPartition as their input.  A new layout
 // is one name here and its branch in choose_routed_layout.

@@ -1,5 +1,5 @@
 """Oracle-bound fuzz of the grouped aggregate's strategy state machine (csrc/dfx_aggregate_strategy.cpp and
-dfx_aggregate_table.cpp; its states are listed above `enum class Phase` in csrc/dfx_aggregate_impl.hpp).
+dfx_aggregate_launch.cpp; its states are listed above `enum class Phase` in csrc/dfx_aggregate_impl.hpp).
 
 Every case of tests/agg_stream_cases.py is a stream of 2^21..2^23 rows in 3-6 ragged host batches whose keys, predicate pass
 rate or nulls CHANGE after the operator has taken its strategy decision (behind the calibration slice, at a batch boundary), run
