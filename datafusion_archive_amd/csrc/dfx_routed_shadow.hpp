@@ -6,6 +6,12 @@
 // major, 8-byte rows {hash image, Float32 bits of the raw operand}, sixteen to a line, partial chunks padded with kTagEmpty,
 // counts[partition x producers + producer] -- and the geometry it was routed for.  A launch whose rows are exactly one window then
 // is ONE kernel (Pass2Rows::narrow8_pred, dfx_k_pass2.hip) that reads the window and evaluates the predicate itself.
+// Who reads it: only a launch that would bind BOTH column shadows itself (launch_rows asks both_shadows_bind before routed_shadow_launch).
+// So agg.key_shadow = 0, agg.value_shadow = 0 and agg.routed_row8 = 0 each switch the reads off for that query exactly as
+// agg.routed_shadow = 0 does -- the two passes run over the 8-byte columns -- and none of them frees or rebuilds anything: the next
+// query under -1 / 1 scans the same windows again.  A pair is built once: a shadow routed for another table geometry than later
+// queries ask with (agg.capacity_log2) stays and serves none of them.  tests/test_gpu_table_query_sequences.py flips each option
+// on a table that holds the shadow.
 // Host only and free of HIP, like dfx_key_shadow.hpp, whose rules these are: the option -1 / 0 / 1, the memory rule on the shadow's
 // full size, one lock per table held across the build, silent drops, refusal for good.  The device work comes in through
 // RoutedShadowDevice: tests/native/routed_shadow_rule.cpp runs the rule with the device stubbed, under the host sanitizers.
