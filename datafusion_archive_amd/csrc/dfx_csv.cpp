@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "dfx_csv_walk.hpp"
+#include "dfx_gather.hpp"
 #include "dfx_relation.hpp"
 
 namespace dfx {
@@ -271,21 +272,11 @@ Status CsvRelation::next(DeviceBatch* out, bool* has) {
       if (col.null_count == 0) col.validity = nullptr;
       continue;
     }
-    auto offs = device_alloc(sizeof(int32_t) * (size_t)(nb + 1), &st);
-    if (!offs) return st;
-    auto tmp = device_alloc(sizeof(uint64_t) * (size_t)(nb / 4096 + 4), &st);
-    if (!tmp) return st;
-    DFX_HIP(launch_scan_i32((const int32_t*)lens[c].get(), (int32_t*)offs.get(), nb, (uint64_t*)tmp.get(), s));
-    int32_t total = 0;
-    DFX_HIP(hipMemcpyAsync(&total, (int32_t*)offs.get() + nb, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    DFX_HIP(hipStreamSynchronize(s));
-    if (total < 0) return Status::Err(DFX_EXECUTION_ERROR, "Utf8 column of a CSV batch exceeds 2 GB (Arrow Utf8 offsets are 32-bit)");
-    auto data = device_alloc((size_t)std::max<int32_t>(total, 8), &st);
-    if (!data) return st;
+    std::shared_ptr<void> offs, data;
+    DFX_RETURN_IF_ERROR(utf8_layout_from_lens((const int32_t*)lens[c].get(), nb, "Utf8 column of a CSV batch", &offs, &data, &col.data_bytes));
     DFX_HIP(launch_csv_utf8_gather(buf, rs, next_record_, nb, c, (const int32_t*)offs.get(), (const uint64_t*)starts[c].get(), (uint8_t*)data.get(), s));
     col.offsets = (const int32_t*)offs.get();
     col.data = (const uint8_t*)data.get();
-    col.data_bytes = total;
     col.null_count = 0;
     col.owners.push_back(offs);
     col.owners.push_back(data);

@@ -1,6 +1,7 @@
 // dfx_filter.cpp -- FilterRelation (src/execution/filter.rs): the predicate's fused programs, next() as a driver over the
 // three ways to a bitmap (a Utf8 term's own, the single-pass kernel, mask -> AND -> scan) and the per-column compaction;
 // its C-ABI constructors and the test hook that reads the bitmap back.
+#include "dfx_gather.hpp"
 #include "dfx_relation.hpp"
 #include "dfx_row_source.hpp"
 
@@ -386,23 +387,14 @@ Status FilterRelation::compact_utf8(const DeviceColumn& ic, const Batch& b, Devi
   if (!lens_c) return st;
   auto starts_c = device_alloc(sizeof(int32_t) * (size_t)(m + 1), &st);
   if (!starts_c) return st;
-  auto offs = device_alloc(sizeof(int32_t) * (size_t)(m + 1), &st);
-  if (!offs) return st;
-  auto tmp2 = device_alloc(sizeof(uint64_t) * (size_t)(m / 4096 + 4), &st);
-  if (!tmp2) return st;
   DFX_HIP(launch_utf8_lengths(ic.offsets, n, (int32_t*)lens.get(), (int32_t*)starts.get(), s));
   DFX_HIP(launch_compact(lens.get(), 4, mask, offsets, n, lens_c.get(), 0, s));
   DFX_HIP(launch_compact(starts.get(), 4, mask, offsets, n, starts_c.get(), 0, s));
-  DFX_HIP(launch_scan_i32((const int32_t*)lens_c.get(), (int32_t*)offs.get(), m, (uint64_t*)tmp2.get(), s));
-  int32_t total = 0;
-  DFX_HIP(hipMemcpyAsync(&total, (int32_t*)offs.get() + m, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  DFX_HIP(hipStreamSynchronize(s));
-  auto bytes = device_alloc((size_t)total + 8, &st);
-  if (!bytes) return st;
+  std::shared_ptr<void> offs, bytes;  // (a subset of a column that fit: the 2 GB rule cannot fire here)
+  DFX_RETURN_IF_ERROR(utf8_layout_from_lens((const int32_t*)lens_c.get(), m, "filtered Utf8 column", &offs, &bytes, &oc->data_bytes));
   DFX_HIP(launch_utf8_gather(ic.data, (const int32_t*)starts_c.get(), (const int32_t*)offs.get(), m, (uint8_t*)bytes.get(), s));
   oc->offsets = (const int32_t*)offs.get();
   oc->data = (const uint8_t*)bytes.get();
-  oc->data_bytes = total;
   oc->owners = {offs, bytes};
   return Status::OK();
 }

@@ -344,5 +344,13 @@ void pool_trim() {
   pin_pool().trim();
 }
 void pool_inject_oom(int n) { dev_pool().inject_oom = n; }
+Status upload_bytes(const void* host, size_t bytes, std::shared_ptr<void>* dev) {
+  Status st;
+  *dev = device_alloc(std::max<size_t>(bytes, 8), &st);
+  if (!*dev) return st;
+  if (bytes) DFX_HIP(hipMemcpyAsync(dev->get(), host, bytes, hipMemcpyHostToDevice, ctx().stream));
+  DFX_HIP(hipStreamSynchronize(ctx().stream));
+  return Status::OK();
+}
 
 }  // namespace dfx

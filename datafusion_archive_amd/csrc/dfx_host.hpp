@@ -114,7 +114,7 @@ Status ensure_init();
 // kernels that read every plan column's validity unconditionally (scan plans, dfx_device.hpp).  nullptr without a device.
 const uint8_t* device_ones_block();
 // measurement: bytes of column data copied host -> device by the uploaders (dfx_counter_get("h2d_bytes"))
-struct Counters {
+struct Counters {  // every field a long long with its name in kCounterNames (dfx_options.cpp): a field of another type must adjust the static_assert there
   long long h2d_bytes = 0;
   long long h2d_staged_bytes = 0;
   long long filter_output_regrows = 0;      // single-pass FilterRelation: batches that kept more rows than their output buffers were sized for
@@ -217,6 +217,13 @@ std::shared_ptr<void> pinned_alloc(size_t bytes, Status* st);
 // ... for work the query does not need (the key shadow): one attempt -- no cached block is released for it, no retry
 std::shared_ptr<void> device_alloc_optional(size_t bytes);
 size_t device_free_bytes();  // ... and what such an allocation can still have (0: the runtime would not say)
+// a small host array (pointer tables, bit offsets, batch starts) as a device buffer of at least 8 bytes: copied on the library's
+// stream and synchronised, so the host array may be a temporary
+Status upload_bytes(const void* host, size_t bytes, std::shared_ptr<void>* dev);
+template <typename T>
+Status upload_vec(const std::vector<T>& v, std::shared_ptr<void>* dev) {
+  return upload_bytes(v.data(), sizeof(T) * v.size(), dev);
+}
 void pool_trim();
 void pool_inject_oom(int n);  // test hook (dfx_set_option "pool.inject_oom"): the next n device allocations fail their first attempt for real
 

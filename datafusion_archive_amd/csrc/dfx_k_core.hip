@@ -38,7 +38,7 @@ uint64_t host_hash_keys(const uint64_t* key, int kw) {
 // ---------------------------------------------------------------------------------------------
 // exclusive scans (tile counts -> offsets; string lengths -> offsets)
 // ---------------------------------------------------------------------------------------------
-constexpr int kScanChunk = 4096;  // elements per block (256 threads x 16)
+// (kScanChunk elements per block, scan_blocks(n) blocks: dfx_scan_rules.hpp)
 
 // block-wide exclusive scan of one value per thread; returns the exclusive prefix, *total = block sum
 DEV uint64_t block_exclusive_scan(uint64_t v, uint64_t* total, uint64_t* lds4) {
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(kBlock) void k_synth_validity(int column_id, uint32
 template <typename TIN, typename TOUT>
 static hipError_t scan_impl(const TIN* in, TOUT* out, int64_t n, uint64_t* tmp, hipStream_t s) {
   Scope sc(KID_SCAN, s, 0);
-  const int64_t nb = n > 0 ? (n + kScanChunk - 1) / kScanChunk : 1;
+  const int64_t nb = scan_blocks(n);  // tmp[nb]: the 64-bit grand total
   hipLaunchKernelGGL((k_scan_local<TIN>), dim3((unsigned)nb), dim3(kBlock), 0, s, in, n, tmp);
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, tmp, nb);
   hipLaunchKernelGGL((k_scan_apply<TIN, TOUT>), dim3((unsigned)nb), dim3(kBlock), 0, s, in, n, tmp, nb, out);

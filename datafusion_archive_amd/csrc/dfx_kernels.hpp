@@ -6,6 +6,7 @@
 #include "dfx_device.hpp"
 #include "dfx_parquet_lz4.hpp"
 #include "dfx_parquet_rle.hpp"
+#include "dfx_scan_rules.hpp"
 #include "dfx_utf8_match.hpp"
 
 namespace dfx {
@@ -81,7 +82,8 @@ hipError_t launch_filter_fused(const DevProgram& P, const DevFastPlan& fast, con
                                uint64_t* mask_words, uint64_t* tile_offsets, uint64_t* sync, const DevFusedOut& O,
                                uint32_t* ctrl, double algo_bytes, hipStream_t s);
 
-// exclusive scan of uint32 counts into uint64 offsets (out[n] = total); tmp: >= (n/4096 + 2) u64
+// exclusive scan of uint32 counts into uint64 offsets (out[n] = total); tmp: >= (n/4096 + 2) u64; afterwards tmp[scan_blocks(n)]
+// (dfx_scan_rules.hpp) holds the 64-bit grand total
 hipError_t launch_scan_u32(const uint32_t* in, uint64_t* out, int64_t n, uint64_t* tmp, hipStream_t s);
 // exclusive scan of int32 lengths into int32 offsets (out[n] = total); tmp as above
 hipError_t launch_scan_i32(const int32_t* in, int32_t* out, int64_t n, uint64_t* tmp, hipStream_t s);

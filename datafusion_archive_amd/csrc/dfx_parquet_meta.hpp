@@ -21,6 +21,7 @@
 #include "../../include/dfx.h"
 #include "dfx_parquet_lz4.hpp"
 #include "dfx_parquet_rle.hpp"
+#include "dfx_scan_rules.hpp"
 
 namespace dfx {
 namespace pq {
@@ -849,9 +850,10 @@ inline Err walk_bodies(const ChunkHeaders& hd, const uint8_t* image, const PqPro
 
 // The bytes of a Utf8 column of one row group must fit Arrow's 32-bit offsets.  The sum is NOT bounded by the chunk: the rows of a
 // dictionary-encoded page take their lengths from the dictionary, so one long entry referenced by many rows sums past 2^31 from a
-// small file.  Both sides sum in 64 bits and ask this before anything is sized by the total.
+// small file.  Both sides sum in 64 bits and ask this before anything is sized by the total.  (The comparison is the library's one
+// rule, dfx_scan_rules.hpp: the sort, the resident table, the CSV source and the filter ask it of their scan's 64-bit total.)
 inline Err utf8_total_error(uint64_t total_bytes, const std::string& where) {
-  if (total_bytes > (uint64_t)INT32_MAX)
+  if (utf8_total_exceeds_offsets(total_bytes))
     return Err{DFX_EXECUTION_ERROR, "Utf8 column of a Parquet row group exceeds 2 GB (Arrow Utf8 offsets are 32-bit): " + where + " holds " +
                                         num((long long)total_bytes) + " bytes"};
   return Err();

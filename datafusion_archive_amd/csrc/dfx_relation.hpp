@@ -52,7 +52,7 @@ class TableScanRelation : public Relation {
 };
 
 // ---- option sets ---------------------------------------------------------------------------------
-struct AggOptions {
+struct AggOptions {  // every field an int with its key in kOptionKeys (dfx_options.cpp): a field of another type must adjust the static_assert there
   int strategy = 0;         // 0 auto, 1 global table only, 2 LDS front cache
   int capacity_log2 = 0;    // 0: default
   int lds_slots = -1;       // -1 auto

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 
+#include "dfx_gather.hpp"
 #include "dfx_relation.hpp"
 
 namespace dfx {
@@ -34,16 +35,6 @@ dfx_runtime_expr column_expr(int i, const SchemaInfo& schema) {
   e.dtype = schema.fields[(size_t)i].dtype;
   e.rebind();
   return e;
-}
-
-template <typename T>
-Status upload_vec(const std::vector<T>& v, std::shared_ptr<void>* dev) {
-  Status st;
-  *dev = device_alloc(std::max<size_t>(sizeof(T) * v.size(), 8), &st);
-  if (!*dev) return st;
-  if (!v.empty()) DFX_HIP(hipMemcpyAsync(dev->get(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, ctx().stream));
-  DFX_HIP(hipStreamSynchronize(ctx().stream));  // v may be a temporary
-  return Status::OK();
 }
 
 }  // namespace
@@ -86,6 +77,8 @@ class SortRelation : public Relation {
   Status sort_by_key(const std::vector<DeviceBatch>& batches, int key, int64_t n, int64_t m, std::shared_ptr<void>* idx);
   // top-k: the rows whose FIRST key is <= the k-th smallest first key (>= k of them, input order kept)
   Status select_candidates(const std::vector<DeviceBatch>& batches, int64_t n, int64_t k, std::shared_ptr<void>* idx, int64_t* m);
+  Status collect_input(std::vector<DeviceBatch>* batches, int64_t* n);
+  Status gather_output(const std::vector<DeviceBatch>& batches, const uint32_t* idx, int64_t n, DeviceBatch* out);
   int64_t limit_ = -1;
   std::unique_ptr<Relation> projected_;
   std::vector<dfx_runtime_expr> keys_;
@@ -262,150 +255,68 @@ Status SortRelation::select_candidates(const std::vector<DeviceBatch>& batches, 
   return Status::OK();
 }
 
+// every non-empty batch of the input (payload columns, then the evaluated keys)
+Status SortRelation::collect_input(std::vector<DeviceBatch>* batches, int64_t* n) {
+  for (;;) {
+    DeviceBatch b;
+    bool got = false;
+    DFX_RETURN_IF_ERROR(projected_->next(&b, &got));
+    if (!got) return Status::OK();
+    if (b.num_rows > 0) {
+      *n += b.num_rows;
+      batches->push_back(std::move(b));
+    }
+  }
+}
+
+// the payload columns of the rows idx[0..n), gathered from the input batches into ONE batch
+Status SortRelation::gather_output(const std::vector<DeviceBatch>& batches, const uint32_t* idx, int64_t n, DeviceBatch* out) {
+  BatchGather gather(batches, idx, n);
+  out->num_rows = n;
+  out->columns.clear();
+  out->columns.resize((size_t)n_payload_);
+  for (int c = 0; c < n_payload_; ++c) {
+    DeviceColumn& oc = out->columns[(size_t)c];
+    oc.dtype = batches[0].columns[(size_t)c].dtype;
+    oc.length = n;
+    std::shared_ptr<void> valid;
+    int64_t zeros = 0;
+    DFX_RETURN_IF_ERROR(gather.validity(c, &valid, &zeros));
+    if (zeros != 0) {  // this operator's rule: a bitmap that turned out all valid (LIMIT cut the nulls off; slices of unknown null count held none) is dropped
+      oc.validity = (const uint8_t*)valid.get();
+      oc.null_count = zeros;
+      oc.owners.push_back(valid);
+    }
+    DFX_RETURN_IF_ERROR(gather.values(c, "sorted Utf8 column", &oc));
+  }
+  DFX_HIP(hipStreamSynchronize(ctx().stream));  // the input batches (and the pointer tables) are released after this
+  return Status::OK();
+}
+
 Status SortRelation::next(DeviceBatch* out, bool* has) {
   *has = false;
   if (!deferred_.ok()) return deferred_;
   if (done_) return Status::OK();
   done_ = true;
   DFX_RETURN_IF_ERROR(ensure_init());
-  hipStream_t s = ctx().stream;
   std::vector<DeviceBatch> batches;
   int64_t n = 0;
-  for (;;) {
-    DeviceBatch b;
-    bool got = false;
-    DFX_RETURN_IF_ERROR(projected_->next(&b, &got));
-    if (!got) break;
-    if (b.num_rows > 0) {
-      n += b.num_rows;
-      batches.push_back(std::move(b));
-    }
-  }
+  DFX_RETURN_IF_ERROR(collect_input(&batches, &n));
   if (n == 0) return Status::OK();  // nothing to sort: Ok(None)
   if (n >= (1ll << 32)) return Status::Err(DFX_NOT_IMPLEMENTED, "ORDER BY over 2^32 or more rows");
   Status st;
-  auto idx0 = device_alloc(sizeof(uint32_t) * (size_t)n, &st);
-  if (!idx0) return st;
-  std::shared_ptr<void> idx = idx0;
-  DFX_HIP(launch_sort_iota((uint32_t*)idx.get(), n, s));
+  std::shared_ptr<void> idx = device_alloc(sizeof(uint32_t) * (size_t)n, &st);
+  if (!idx) return st;
+  DFX_HIP(launch_sort_iota((uint32_t*)idx.get(), n, ctx().stream));
   int64_t m = n;         // rows that take part in the sort
-  int64_t n_out = n;     // rows that are emitted
+  int64_t n_out = n;     // rows that are emitted: the first n_out of the sorted permutation
   if (limit_ >= 0 && limit_ < n) {
     n_out = limit_;
     if (n_out == 0) return Status::OK();
     if (limit_ <= n / 8) DFX_RETURN_IF_ERROR(select_candidates(batches, n, limit_, &idx, &m));  // else: sort everything
   }
   for (int k = (int)keys_.size() - 1; k >= 0; --k) DFX_RETURN_IF_ERROR(sort_by_key(batches, k, n, m, &idx));
-  n = n_out;  // from here on: the rows that are emitted (the first n_out of the sorted permutation)
-  // (batch, row) of every output row, then gather the payload columns from the input batches
-  const int nb = (int)batches.size();
-  std::vector<uint64_t> starts((size_t)nb + 1, 0);
-  for (int b = 0; b < nb; ++b) starts[(size_t)b + 1] = starts[(size_t)b] + (uint64_t)batches[(size_t)b].num_rows;
-  std::shared_ptr<void> dstarts;
-  DFX_RETURN_IF_ERROR(upload_vec(starts, &dstarts));
-  auto loc = device_alloc(sizeof(uint64_t) * (size_t)n, &st);
-  if (!loc) return st;
-  DFX_HIP(launch_sort_locate((const uint32_t*)idx.get(), n, (const uint64_t*)dstarts.get(), nb, (uint64_t*)loc.get(), s));
-  out->num_rows = n;
-  out->columns.clear();
-  out->columns.resize((size_t)n_payload_);
-  const size_t words = (size_t)(n + 63) / 64;
-  for (int c = 0; c < n_payload_; ++c) {
-    DeviceColumn& oc = out->columns[(size_t)c];
-    const int dt = batches[0].columns[(size_t)c].dtype;
-    oc.dtype = dt;
-    oc.length = n;
-    bool any_nulls = false;
-    for (const DeviceBatch& b : batches)
-      if (b.columns[(size_t)c].validity && b.columns[(size_t)c].null_count != 0) any_nulls = true;
-    if (any_nulls) {
-      std::vector<const uint8_t*> vb;
-      std::vector<int64_t> vo;
-      for (const DeviceBatch& b : batches) {
-        const DeviceColumn& ic = b.columns[(size_t)c];
-        vb.push_back((ic.validity && ic.null_count != 0) ? ic.validity : nullptr);
-        vo.push_back(ic.bit_offset);
-      }
-      std::shared_ptr<void> dvb, dvo;
-      DFX_RETURN_IF_ERROR(upload_vec(vb, &dvb));
-      DFX_RETURN_IF_ERROR(upload_vec(vo, &dvo));
-      auto valid = device_alloc(words * 8 + 8, &st);
-      if (!valid) return st;
-      auto zeros = device_alloc(sizeof(uint64_t), &st);
-      if (!zeros) return st;
-      DFX_HIP(hipMemsetAsync(zeros.get(), 0, sizeof(uint64_t), s));
-      DFX_HIP(launch_gather_bits((const uint8_t* const*)dvb.get(), (const int64_t*)dvo.get(), (const uint64_t*)loc.get(), n,
-                                 (uint64_t*)valid.get(), (uint64_t*)zeros.get(), s));
-      uint64_t nz = 0;
-      DFX_HIP(hipMemcpyAsync(&nz, zeros.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-      DFX_HIP(hipStreamSynchronize(s));
-      if (nz) {
-        oc.validity = (const uint8_t*)valid.get();
-        oc.null_count = (int64_t)nz;
-        oc.owners.push_back(valid);
-      }
-    }
-    if (dt == DFX_UTF8) {
-      std::vector<const int32_t*> ob;
-      std::vector<const uint8_t*> db;
-      for (const DeviceBatch& b : batches) {
-        ob.push_back(b.columns[(size_t)c].offsets);
-        db.push_back(b.columns[(size_t)c].data);
-      }
-      std::shared_ptr<void> dob, ddb;
-      DFX_RETURN_IF_ERROR(upload_vec(ob, &dob));
-      DFX_RETURN_IF_ERROR(upload_vec(db, &ddb));
-      auto lens = device_alloc(sizeof(int32_t) * (size_t)(n + 1), &st);
-      if (!lens) return st;
-      auto offs = device_alloc(sizeof(int32_t) * (size_t)(n + 1), &st);
-      if (!offs) return st;
-      auto tmp = device_alloc(sizeof(uint64_t) * (size_t)(n / 4096 + 4), &st);
-      if (!tmp) return st;
-      DFX_HIP(launch_gather_utf8_lens((const int32_t* const*)dob.get(), (const uint64_t*)loc.get(), n, (int32_t*)lens.get(), s));
-      DFX_HIP(launch_scan_i32((const int32_t*)lens.get(), (int32_t*)offs.get(), n, (uint64_t*)tmp.get(), s));
-      int32_t total = 0;
-      DFX_HIP(hipMemcpyAsync(&total, (int32_t*)offs.get() + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      DFX_HIP(hipStreamSynchronize(s));
-      if (total < 0) return Status::Err(DFX_EXECUTION_ERROR, "sorted Utf8 column exceeds 2 GB (Arrow Utf8 offsets are 32-bit)");
-      auto data = device_alloc((size_t)std::max<int32_t>(total, 8), &st);
-      if (!data) return st;
-      DFX_HIP(launch_gather_utf8_copy((const int32_t* const*)dob.get(), (const uint8_t* const*)ddb.get(), (const uint64_t*)loc.get(), n,
-                                      (const int32_t*)offs.get(), (uint8_t*)data.get(), s));
-      oc.offsets = (const int32_t*)offs.get();
-      oc.data = (const uint8_t*)data.get();
-      oc.data_bytes = total;
-      oc.owners.push_back(offs);
-      oc.owners.push_back(data);
-    } else if (dt == DFX_BOOLEAN) {
-      std::vector<const uint8_t*> vb;
-      std::vector<int64_t> vo;
-      for (const DeviceBatch& b : batches) {
-        vb.push_back((const uint8_t*)b.columns[(size_t)c].values);
-        vo.push_back(b.columns[(size_t)c].bit_offset);
-      }
-      std::shared_ptr<void> dvb, dvo;
-      DFX_RETURN_IF_ERROR(upload_vec(vb, &dvb));
-      DFX_RETURN_IF_ERROR(upload_vec(vo, &dvo));
-      auto vals = device_alloc(words * 8 + 8, &st);
-      if (!vals) return st;
-      DFX_HIP(launch_gather_bits((const uint8_t* const*)dvb.get(), (const int64_t*)dvo.get(), (const uint64_t*)loc.get(), n,
-                                 (uint64_t*)vals.get(), nullptr, s));
-      oc.values = vals.get();
-      oc.owners.push_back(vals);
-    } else {
-      std::vector<const void*> vb;
-      for (const DeviceBatch& b : batches) vb.push_back(b.columns[(size_t)c].values);
-      std::shared_ptr<void> dvb;
-      DFX_RETURN_IF_ERROR(upload_vec(vb, &dvb));
-      const int w = dtype_width(dt);
-      auto vals = device_alloc((size_t)n * (size_t)w, &st);
-      if (!vals) return st;
-      DFX_HIP(launch_gather_fixed((const void* const*)dvb.get(), (const uint64_t*)loc.get(), n, w, vals.get(), s));
-      oc.values = vals.get();
-      oc.owners.push_back(vals);
-    }
-  }
-  DFX_HIP(hipStreamSynchronize(s));  // the input batches (and the pointer tables) are released after this
+  DFX_RETURN_IF_ERROR(gather_output(batches, (const uint32_t*)idx.get(), n_out, out));
   *has = true;
   return Status::OK();
 }

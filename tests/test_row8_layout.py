@@ -19,6 +19,6 @@ def test_row8_layout_program(tmp_path):
 def test_row8_option_and_counter_are_wired():
     from datafusion_archive_amd import build as B
 
-    table = open(os.path.join(B.CSRC, "dfx_table.cpp")).read()
+    table = open(os.path.join(B.CSRC, "dfx_options.cpp")).read()
     assert '"agg.routed_row8"' in table and '"agg_row8_launches"' in table
     assert "int routed_row8 = -1;" in open(os.path.join(B.CSRC, "dfx_relation.hpp")).read()
