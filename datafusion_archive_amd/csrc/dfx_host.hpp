@@ -200,6 +200,11 @@ struct Counters {  // every field a long long with its name in kCounterNames (df
   long long parquet_write_rle_level_pages = 0;         // ... pages of OPTIONAL columns whose levels are one RLE run (all valid / all null)
   long long parquet_write_bitpacked_level_pages = 0;   // ... whose levels are one bit-packed run (valid and null rows)
   long long parquet_write_row_groups = 0;              // row groups written
+  long long parquet_write_dict_pages = 0;              // "dictionary" > 0: dictionary pages written (one per chunk that held the mode for a launch)
+  long long parquet_write_dict_entries = 0;            // ... the entries they hold
+  long long parquet_write_dict_index_pages = 0;        // ... data pages of dictionary indices (counted in parquet_write_pages as well)
+  long long parquet_write_dict_rle_index_pages = 0;    // ... of them, pages whose indices are one RLE run (all equal)
+  long long parquet_write_dict_fallback_chunks = 0;    // ... chunks that left dictionary mode for PLAIN, a fallback in the first launch included
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;

@@ -142,6 +142,11 @@ constexpr CounterName kCounterNames[] = {
     {"parquet_write_rle_level_pages",       &Counters::parquet_write_rle_level_pages},
     {"parquet_write_bitpacked_level_pages", &Counters::parquet_write_bitpacked_level_pages},
     {"parquet_write_row_groups",            &Counters::parquet_write_row_groups},
+    {"parquet_write_dict_pages",            &Counters::parquet_write_dict_pages},
+    {"parquet_write_dict_entries",          &Counters::parquet_write_dict_entries},
+    {"parquet_write_dict_index_pages",      &Counters::parquet_write_dict_index_pages},
+    {"parquet_write_dict_rle_index_pages",  &Counters::parquet_write_dict_rle_index_pages},
+    {"parquet_write_dict_fallback_chunks",  &Counters::parquet_write_dict_fallback_chunks},
     {"xchg_calls",                          &Counters::xchg_calls},
     {"xchg_local_us",                       &Counters::xchg_local_us},
     {"xchg_wait_peers_us",                  &Counters::xchg_wait_peers_us},

@@ -275,8 +275,8 @@ struct ColumnSpec {
 };
 inline const char* created_by() { return "datafusion_archive_amd dfx_parquet_write (D13)"; }
 
-// Pages go in row group by row group, column by column, in row order: begin_row_group, per column begin_chunk + add_page*, then
-// end_row_group.  `put` receives the file's bytes in order (false: the write failed; the writer stops and every later call fails).
+// Pages go in row group by row group, column by column, in row order: begin_row_group, per column begin_chunk + add_page* (for a
+// dictionary chunk, dfx_parquet_dict_enc.hpp: add_dictionary_page first, and the encoding of every page), then end_row_group.  `put` receives the file's bytes in order (false: the write failed; the writer stops and every later call fails).
 class FileWriter {
  public:
   typedef bool (*Put)(void* ctx, const void* p, size_t n);
@@ -291,9 +291,20 @@ class FileWriter {
     k.data_page_offset = (int64_t)bytes_;
     groups_.back().chunks.push_back(k);
   }
-  bool add_page(int64_t num_values, int64_t non_null, const void* body, size_t body_bytes) {
+  // the chunk's first page: the PLAIN values of its dictionary, in id order (before any add_page of the chunk)
+  bool add_dictionary_page(int64_t entries, const void* body, size_t body_bytes) {
     header_.clear();
-    write_page_header((int32_t)body_bytes, (int32_t)num_values, &header_);
+    write_dictionary_page_header((int32_t)body_bytes, (int32_t)entries, &header_);
+    ChunkInfo& k = groups_.back().chunks.back();
+    k.has_dictionary = true;
+    k.dictionary_page_offset = (int64_t)bytes_;
+    k.total_size += (int64_t)(header_.size() + body_bytes);
+    k.data_page_offset = (int64_t)(bytes_ + header_.size() + body_bytes);
+    return emit(header_.data(), header_.size()) && emit(body, body_bytes);
+  }
+  bool add_page(int64_t num_values, int64_t non_null, const void* body, size_t body_bytes, int encoding = ENCODING_PLAIN) {
+    header_.clear();
+    write_page_header((int32_t)body_bytes, (int32_t)num_values, &header_, encoding);
     ChunkInfo& k = groups_.back().chunks.back();
     k.num_values += num_values;
     k.null_count += num_values - non_null;

@@ -1,6 +1,6 @@
 // dfx_parquet_thrift_write.hpp -- the writing side of thrift's compact protocol and, on top of it, the Parquet structures the
 // writer (deviation D13: dfx_parquet_write.cpp) puts into a file: PageHeader / DataPageHeader, SchemaElement with its logical type,
-// ColumnMetaData, ColumnChunk, RowGroup, FileMetaData.  Free of HIP.  It is the mirror of the reader in dfx_parquet_meta.hpp: what
+// ColumnMetaData, ColumnChunk, RowGroup, FileMetaData; DictionaryPageHeader for the chunks written under the sink's "dictionary" option.  Free of HIP.  It is the mirror of the reader in dfx_parquet_meta.hpp: what
 // is written here, that reader parses back (tests/native/parquet_write_check.cpp holds the two against each other without pyarrow).
 //
 //   varint    7 bits per byte, least significant first, the high bit set on every byte but the last
@@ -90,7 +90,7 @@ class ThriftWriter {
 
 // ---- the Parquet structures (parquet.thrift; only the fields this writer sets) ---------------------------------------------------
 enum : int { PHYS_BOOLEAN = 0, PHYS_INT32 = 1, PHYS_INT64 = 2, PHYS_FLOAT = 4, PHYS_DOUBLE = 5, PHYS_BYTE_ARRAY = 6 };
-enum : int { ENCODING_PLAIN = 0, ENCODING_RLE = 3 };
+enum : int { ENCODING_PLAIN = 0, ENCODING_RLE = 3, ENCODING_RLE_DICTIONARY = 8 };
 enum : int { REP_REQUIRED = 0, REP_OPTIONAL = 1 };
 enum : int { CONV_NONE = -1, CONV_UTF8 = 0, CONV_UINT_8 = 11, CONV_UINT_16 = 12, CONV_UINT_32 = 13, CONV_UINT_64 = 14, CONV_INT_8 = 15, CONV_INT_16 = 16,
              CONV_INT_32 = 17 };
@@ -107,8 +107,9 @@ struct LeafSchema {
 };
 
 // PageHeader { 1 type = DATA_PAGE, 2 uncompressed_page_size, 3 compressed_page_size, 5 DataPageHeader { 1 num_values, 2 encoding = PLAIN,
-// 3 definition_level_encoding = RLE, 4 repetition_level_encoding = RLE } }: a V1 data page of an UNCOMPRESSED chunk, no CRC, no statistics
-inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out) {
+// 3 definition_level_encoding = RLE, 4 repetition_level_encoding = RLE } }: a V1 data page of an UNCOMPRESSED chunk, no CRC, no statistics;
+// encoding: PLAIN, or RLE_DICTIONARY for a page of dictionary indices
+inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out, int encoding = ENCODING_PLAIN) {
   ThriftWriter t(out);
   t.begin_struct(0);
   t.i32(1, 0);
@@ -116,9 +117,23 @@ inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vecto
   t.i32(3, body_bytes);
   t.begin_struct(5);
   t.i32(1, num_values);
-  t.i32(2, ENCODING_PLAIN);
+  t.i32(2, encoding);
   t.i32(3, ENCODING_RLE);
   t.i32(4, ENCODING_RLE);
+  t.end_struct();
+  t.end_struct();
+}
+// PageHeader { 1 type = DICTIONARY_PAGE, 2 uncompressed_page_size, 3 compressed_page_size, 7 DictionaryPageHeader { 1 num_values,
+// 2 encoding = PLAIN } }: the first page of a dictionary-encoded chunk
+inline void write_dictionary_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out) {
+  ThriftWriter t(out);
+  t.begin_struct(0);
+  t.i32(1, 2);
+  t.i32(2, body_bytes);
+  t.i32(3, body_bytes);
+  t.begin_struct(7);
+  t.i32(1, num_values);
+  t.i32(2, ENCODING_PLAIN);
   t.end_struct();
   t.end_struct();
 }
@@ -155,17 +170,21 @@ struct ChunkInfo {  // one column chunk of a row group, as the footer records it
   int64_t num_values = 0, null_count = 0;
   int64_t total_size = 0;  // headers + bodies of its pages (UNCOMPRESSED: both sizes)
   int64_t data_page_offset = 0;
+  bool has_dictionary = false;  // the chunk starts with a dictionary page: encodings PLAIN, RLE, RLE_DICTIONARY; total_size counts it
+  int64_t dictionary_page_offset = 0;
 };
 // ColumnChunk { 2 file_offset, 3 ColumnMetaData { 1 type, 2 encodings, 3 path_in_schema, 4 codec = UNCOMPRESSED, 5 num_values,
-// 6 total_uncompressed_size, 7 total_compressed_size, 9 data_page_offset, 12 Statistics { 3 null_count } } }
+// 6 total_uncompressed_size, 7 total_compressed_size, 9 data_page_offset, 11 dictionary_page_offset (a chunk with a dictionary page),
+// 12 Statistics { 3 null_count } } }
 inline void write_column_chunk(ThriftWriter& t, const ChunkInfo& c) {
   t.begin_struct(0);
   t.i64(2, c.data_page_offset);
   t.begin_struct(3);
   t.i32(1, c.physical);
-  t.list(2, TW_I32, c.optional ? 2 : 1);
+  t.list(2, TW_I32, c.has_dictionary ? 3 : c.optional ? 2 : 1);
   t.zigzag(ENCODING_PLAIN);
-  if (c.optional) t.zigzag(ENCODING_RLE);
+  if (c.optional || c.has_dictionary) t.zigzag(ENCODING_RLE);
+  if (c.has_dictionary) t.zigzag(ENCODING_RLE_DICTIONARY);
   t.list(3, TW_BINARY, 1);
   t.binary_value(c.name);
   t.i32(4, 0);
@@ -173,6 +192,7 @@ inline void write_column_chunk(ThriftWriter& t, const ChunkInfo& c) {
   t.i64(6, c.total_size);
   t.i64(7, c.total_size);
   t.i64(9, c.data_page_offset);
+  if (c.has_dictionary) t.i64(11, c.dictionary_page_offset);
   t.begin_struct(12);
   t.i64(3, c.null_count);
   t.end_struct();

@@ -10,6 +10,14 @@
 // group's encoded bytes.  At the close every column's pages go to the file as [header][body], straight from the pinned buffers; the
 // host writes headers and the footer (dfx_parquet_thrift_write.hpp) and touches no value.  The bytes go to `filename` +
 // ".dfx-partial" and are renamed at the end.
+//
+// Under "dictionary" = N > 0 every non-Boolean column chunk starts in dictionary mode (dfx_parquet_dict_enc.hpp has the format and the
+// per-launch decision, dfx_k_parquet_write_dict.hip the kernels).  The columns of a launch whose chunks are in that mode take a chain of
+// their own (encode_dict_columns); the decision is made on the device and comes back with the page table.  A column that falls back in
+// a launch is encoded PLAIN by the ordinary chain, in the same call, with the Boolean columns and the columns that fell back earlier:
+// that launch pays the ordinary chain's two synchronisations on top -- once in a chunk's life, which for a column that never fits its
+// dictionary is once per row group.  The dictionary bodies stay on the
+// device until the group closes: one copy and one synchronisation more per row group.  With the option at 0 none of this runs.
 #include <errno.h>
 #include <stdio.h>
 #include <string.h>
@@ -28,6 +36,8 @@ using namespace pqw;
 struct PqwOptions {
   int64_t row_group_rows = kDefaultRowGroupRows;
   int64_t page_rows = kDefaultPageRows;
+  int64_t dictionary = 0;             // N: the most entries of a chunk's dictionary; 0: PLAIN pages only
+  int64_t dictionary_hash_bits = 64;  // (debug) the Utf8 hash is cut to this many bits, so that a test can make strings collide
 };
 
 Status parse_options(const dfx_option* options, int32_t n_options, PqwOptions* o) {
@@ -40,10 +50,20 @@ Status parse_options(const dfx_option* options, int32_t n_options, PqwOptions* o
     } else if (!strcmp(key, "page_rows")) {
       if (!page_rows_ok(v)) return Status::Err(DFX_GENERAL, strfmt("page_rows = %lld: a multiple of 64 from 64 to 2^30", (long long)v));
       o->page_rows = v;
+    } else if (!strcmp(key, "dictionary")) {
+      if (!dictionary_ok(v)) return Status::Err(DFX_GENERAL, strfmt("dictionary = %lld: 0 (none) or the most entries of a chunk's dictionary, 1 to 2^20", (long long)v));
+      o->dictionary = v;
+    } else if (!strcmp(key, "dictionary_hash_bits")) {
+      if (!dictionary_hash_bits_ok(v)) return Status::Err(DFX_GENERAL, strfmt("dictionary_hash_bits = %lld: 1 to 64", (long long)v));
+      o->dictionary_hash_bits = v;
     } else {
       return Status::Err(DFX_GENERAL, std::string("unknown option ") + key);
     }
   }
+  // (the dictionary chain keeps a word per row and column of a launch; a page above kLaunchRows rows is a launch of its own, up to 2^30 rows)
+  if (o->dictionary > 0 && o->page_rows > kLaunchRows)
+    return Status::Err(DFX_GENERAL, strfmt("dictionary = %lld with page_rows = %lld: dictionary encoding takes pages of at most 2^20 rows", (long long)o->dictionary,
+                                           (long long)o->page_rows));
   return Status::OK();
 }
 
@@ -69,6 +89,13 @@ class ParquetSink {
     int64_t num_values, non_null;
     const uint8_t* body;  // in one of held_buffers_
     size_t bytes;
+    int encoding;  // ENCODING_PLAIN / ENCODING_RLE_DICTIONARY
+  };
+  struct DictColumn {  // a column's chunk of the open row group under the "dictionary" option
+    bool active = false;  // in dictionary mode (never: Boolean columns, the option at 0)
+    int64_t launches = 0;  // launches held in dictionary mode: > 0, the chunk gets a dictionary page
+    uint64_t entries = 0, body_bytes = 0, body_cap = 0;
+    std::shared_ptr<void> slots, entry_off, body;  // device: the table, Utf8 entry offsets, the dictionary page's body
   };
   static std::vector<ColumnSpec> specs(const SchemaInfo& sc) {
     std::vector<ColumnSpec> out;
@@ -89,7 +116,11 @@ class ParquetSink {
   }
   Status io_error() const { return io_.ok() ? Status::Err(DFX_IO_ERROR, "write to " + tmp_ + " failed") : io_; }
   Status encode_rows(const DeviceBatch& b, int64_t r0, int64_t n);
-  Status encode_columns(const DeviceBatch& b, int c0, int nc, int64_t r0, int64_t n);
+  Status encode_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n);
+  Status encode_dict_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n);
+  Status plan_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n, DevPqwPlan* plan, bool* any_boolean);
+  Status check_pages(const PqwPage* pt, const DevPqwPlan& plan, int k, int col, int64_t n);
+  Status open_group();
   Status close_group();
 
   std::unique_ptr<Relation> in_;
@@ -102,28 +133,28 @@ class ParquetSink {
   int64_t group_rows_ = 0;                          // rows of the open row group
   std::vector<std::vector<HeldPage>> held_;          // ... its encoded pages, column by column
   std::vector<std::shared_ptr<void>> held_buffers_;  // ... the pinned buffers they lie in
+  std::vector<DictColumn> dict_;                     // ... its dictionary chunks ("dictionary" > 0)
+  std::shared_ptr<void> dict_states_;                // PqwdState per column, on the device
+  uint64_t dict_slots_ = 0;                          // slots of a chunk's table
 };
 
-// one launch chain over rows [r0, r0 + n) of columns [c0, c0 + nc) of the batch
-Status ParquetSink::encode_columns(const DeviceBatch& b, int c0, int nc, int64_t r0, int64_t n) {
-  hipStream_t s = ctx().stream;
+// the plan of a launch chain over rows [r0, r0 + n) of the nc columns cols[] of the batch
+Status ParquetSink::plan_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n, DevPqwPlan* plan, bool* any_boolean) {
   const SchemaInfo& sc = in_->schema();
-  Status st;
-  DevPqwPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  plan.n_cols = nc;
-  plan.rows = n;
-  plan.page_rows = opt_.page_rows;
-  plan.n_tiles = tiles_of(n);
-  plan.n_pages = pages_of(n, opt_.page_rows);
-  bool any_boolean = false;
+  memset(plan, 0, sizeof(*plan));
+  plan->n_cols = nc;
+  plan->rows = n;
+  plan->page_rows = opt_.page_rows;
+  plan->n_tiles = tiles_of(n);
+  plan->n_pages = pages_of(n, opt_.page_rows);
+  *any_boolean = false;
   for (int k = 0; k < nc; ++k) {
-    const DeviceColumn& col = b.columns[(size_t)(c0 + k)];
-    DevPqwCol& d = plan.col[k];
-    if (col.absent || col.length < r0 + n || col.dtype != sc.fields[(size_t)(c0 + k)].dtype)
+    const DeviceColumn& col = b.columns[(size_t)cols[k]];
+    DevPqwCol& d = plan->col[k];
+    if (col.absent || col.length < r0 + n || col.dtype != sc.fields[(size_t)cols[k]].dtype)
       return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a column of the batch is absent, short or not of the schema's type");
     d.dtype = (uint8_t)col.dtype;
-    d.optional = sc.fields[(size_t)(c0 + k)].nullable ? 1 : 0;
+    d.optional = sc.fields[(size_t)cols[k]].nullable ? 1 : 0;
     d.validity = (col.validity && col.null_count != 0) ? col.validity : nullptr;
     d.bit_offset = col.bit_offset + r0;
     if (col.dtype == DFX_UTF8) {
@@ -132,11 +163,37 @@ Status ParquetSink::encode_columns(const DeviceBatch& b, int c0, int nc, int64_t
       d.data = col.data;
     } else if (col.dtype == DFX_BOOLEAN) {
       d.values = col.values;
-      any_boolean = true;
+      *any_boolean = true;
     } else {
       d.values = (const uint8_t*)col.values + (size_t)r0 * (size_t)dtype_width(col.dtype);
     }
   }
+  return Status::OK();
+}
+
+// what the host refuses of column cols[k]'s pages of a launch: nulls in a REQUIRED column, a page the i32 rule refuses
+Status ParquetSink::check_pages(const PqwPage* pt, const DevPqwPlan& plan, int k, int col, int64_t n) {
+  const Field& f = in_->schema().fields[(size_t)col];
+  for (int64_t p = 0; p < plan.n_pages; ++p) {
+    const PqwPage& g = pt[(int64_t)k * plan.n_pages + p];
+    const int64_t page_n = std::min<int64_t>(opt_.page_rows, n - p * opt_.page_rows);
+    if (!f.nullable && (int64_t)g.non_null != page_n)
+      return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: column '%s' is not nullable (REQUIRED) and its batch holds %lld nulls in a page of %lld rows",
+                                                     f.name.c_str(), (long long)(page_n - (int64_t)g.non_null), (long long)page_n));
+    if (g.flags & PQW_PAGE_TOO_LARGE || !body_fits(g.level_bytes, g.val_bytes))
+      return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: a page of column '%s' takes %llu bytes; a page header holds sizes below 2^31 - 1 (smaller page_rows)",
+                                                     f.name.c_str(), (unsigned long long)(g.level_bytes + g.val_bytes)));
+  }
+  return Status::OK();
+}
+
+// one launch chain of PLAIN pages over rows [r0, r0 + n) of the nc columns cols[] of the batch
+Status ParquetSink::encode_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n) {
+  hipStream_t s = ctx().stream;
+  Status st;
+  DevPqwPlan plan;
+  bool any_boolean = false;
+  DFX_RETURN_IF_ERROR(plan_columns(b, cols, nc, r0, n, &plan, &any_boolean));
   const int64_t n_tiles = plan.n_tiles * nc, n_pages = plan.n_pages * nc;
   auto tiles = device_alloc(sizeof(PqwTile) * (size_t)n_tiles, &st);
   if (!tiles) return st;
@@ -152,18 +209,7 @@ Status ParquetSink::encode_columns(const DeviceBatch& b, int c0, int nc, int64_t
   DFX_HIP(hipMemcpyAsync(table.get(), d_pages, sizeof(PqwPage) * (size_t)(n_pages + 1), hipMemcpyDeviceToHost, s));
   DFX_HIP(hipStreamSynchronize(s));  // the page table: the one read-back of the launch
   const PqwPage* pt = (const PqwPage*)table.get();
-  for (int k = 0; k < nc; ++k)
-    for (int64_t p = 0; p < plan.n_pages; ++p) {
-      const PqwPage& g = pt[(int64_t)k * plan.n_pages + p];
-      const int64_t page_n = std::min<int64_t>(opt_.page_rows, n - p * opt_.page_rows);
-      const Field& f = sc.fields[(size_t)(c0 + k)];
-      if (!f.nullable && (int64_t)g.non_null != page_n)
-        return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: column '%s' is not nullable (REQUIRED) and its batch holds %lld nulls in a page of %lld rows",
-                                                       f.name.c_str(), (long long)(page_n - (int64_t)g.non_null), (long long)page_n));
-      if (g.flags & PQW_PAGE_TOO_LARGE || !body_fits(g.level_bytes, g.val_bytes))
-        return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: a page of column '%s' takes %llu bytes; a page header holds sizes below 2^31 - 1 (smaller page_rows)",
-                                                       f.name.c_str(), (unsigned long long)(g.level_bytes + g.val_bytes)));
-    }
+  for (int k = 0; k < nc; ++k) DFX_RETURN_IF_ERROR(check_pages(pt, plan, k, cols[k], n));
   const uint64_t total = pt[n_pages].base;
   auto out = device_alloc((size_t)total + 16, &st);
   if (!out) return st;
@@ -187,26 +233,196 @@ Status ParquetSink::encode_columns(const DeviceBatch& b, int c0, int nc, int64_t
       h.non_null = (int64_t)g.non_null;
       h.body = (const uint8_t*)host.get() + g.base;
       h.bytes = (size_t)body;
-      held_[(size_t)(c0 + k)].push_back(h);
+      h.encoding = ENCODING_PLAIN;
+      held_[(size_t)cols[k]].push_back(h);
       if (g.kind == LEVELS_MIXED) ++counters().parquet_write_bitpacked_level_pages;
       else if (g.kind != LEVELS_NONE) ++counters().parquet_write_rle_level_pages;
     }
   return Status::OK();
 }
 
-Status ParquetSink::encode_rows(const DeviceBatch& b, int64_t r0, int64_t n) {
-  const int n_cols = (int)b.columns.size();
-  for (int c0 = 0; c0 < n_cols; c0 += kPqwMaxCols) DFX_RETURN_IF_ERROR(encode_columns(b, c0, std::min(kPqwMaxCols, n_cols - c0), r0, n));
+// one launch chain over rows [r0, r0 + n) of the nc columns cols[] of the batch, whose chunks are all in dictionary mode: pages of
+// dictionary indices for the columns that stay in it; a column that falls back is marked (dict_[col].active) and left to the caller
+Status ParquetSink::encode_dict_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n) {
+  hipStream_t s = ctx().stream;
+  const size_t n_schema = dict_.size();
+  Status st;
+  DevPqwdPlan plan;
+  bool any_boolean = false;
+  DFX_RETURN_IF_ERROR(plan_columns(b, cols, nc, r0, n, &plan.base, &any_boolean));
+  memset(plan.dict, 0, sizeof(plan.dict));
+  plan.hash_mask = opt_.dictionary_hash_bits >= 64 ? ~0ull : (1ull << opt_.dictionary_hash_bits) - 1ull;
+  PqwdState* d_states = (PqwdState*)dict_states_.get();
+  for (int k = 0; k < nc; ++k) {
+    DictColumn& dc = dict_[(size_t)cols[k]];
+    DevPqwdCol& d = plan.dict[k];
+    d.slots = (PqwdSlot*)dc.slots.get();
+    d.state = d_states + cols[k];
+    d.body = (uint8_t*)dc.body.get();
+    d.entry_off = (uint32_t*)dc.entry_off.get();
+    d.body_cap = dc.body_cap;
+    d.mask = (uint32_t)(dict_slots_ - 1);
+    d.limit = (uint32_t)opt_.dictionary;
+  }
+  const int64_t n_tiles = plan.base.n_tiles * nc, n_pages = plan.base.n_pages * nc;
+  auto slot_of_row = device_alloc(sizeof(uint32_t) * (size_t)n * (size_t)nc, &st);
+  if (!slot_of_row) return st;
+  auto tiles = device_alloc(sizeof(PqwdTile) * (size_t)n_tiles, &st);
+  if (!tiles) return st;
+  const size_t table_bytes = sizeof(PqwPage) * (size_t)(n_pages + 1) + sizeof(uint64_t);
+  auto pages = device_alloc(table_bytes, &st);
+  if (!pages) return st;
+  auto table = pinned_alloc(table_bytes + sizeof(PqwdState) * n_schema, &st);  // the page table, the control word, every column's state
+  if (!table) return st;
+  PqwPage* d_pages = (PqwPage*)pages.get();
+  uint64_t* ctrl = (uint64_t*)(d_pages + n_pages + 1);
+  const PqwPage* pt = (const PqwPage*)table.get();
+  const uint64_t* hc = (const uint64_t*)(pt + n_pages + 1);
+  const PqwdState* states = (const PqwdState*)(hc + 1);
+  DFX_HIP(hipMemsetAsync(ctrl, 0, sizeof(uint64_t), s));
+  DFX_HIP(launch_pqwd_measure(plan, (uint32_t*)slot_of_row.get(), (PqwdTile*)tiles.get(), d_pages, s));
+  DFX_HIP(launch_pqw_bases(d_pages, n_pages, s));
+  DFX_HIP(hipMemcpyAsync(table.get(), d_pages, sizeof(PqwPage) * (size_t)(n_pages + 1), hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipMemcpyAsync((void*)states, d_states, sizeof(PqwdState) * n_schema, hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));  // the page table and, with it, every column's mode for this launch
+  std::vector<std::shared_ptr<void>> outgrown;  // dictionary bodies being copied from: alive until the launch's second synchronisation
+  bool any_stayed = false;
+  for (int k = 0; k < nc; ++k) {
+    DictColumn& dc = dict_[(size_t)cols[k]];
+    const PqwdState& hs = states[cols[k]];
+    if (hs.mode != PQWD_MODE_DICT) {  // fell back: PLAIN from this launch to the chunk's end
+      dc.active = false;
+      ++counters().parquet_write_dict_fallback_chunks;
+      continue;
+    }
+    any_stayed = true;
+    if (hs.entries < dc.entries || hs.entries > (uint64_t)opt_.dictionary || hs.body_bytes < dc.body_bytes || !body_fits(0, hs.body_bytes) ||
+        hs.entries_before != dc.entries || hs.body_before != dc.body_bytes)
+      return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a dictionary's state on the device does not follow from the host's");
+    DFX_RETURN_IF_ERROR(check_pages(pt, plan.base, k, cols[k], n));
+    if (hs.body_bytes > dc.body_cap) {  // the body grows: the entries so far move, on the stream, before commit appends
+      const uint64_t cap = std::max<uint64_t>({hs.body_bytes, 2 * dc.body_cap, 4096});
+      auto grown = device_alloc((size_t)cap, &st);
+      if (!grown) return st;
+      if (dc.body_bytes) DFX_HIP(hipMemcpyAsync(grown.get(), dc.body.get(), (size_t)dc.body_bytes, hipMemcpyDeviceToDevice, s));
+      outgrown.push_back(dc.body);
+      dc.body = grown;
+      dc.body_cap = cap;
+      plan.dict[k].body = (uint8_t*)grown.get();
+      plan.dict[k].body_cap = cap;
+    }
+    dc.entries = hs.entries;
+    dc.body_bytes = hs.body_bytes;
+    ++dc.launches;
+  }
+  if (!any_stayed) return Status::OK();
+  const uint64_t total = pt[n_pages].base;
+  auto out = device_alloc((size_t)total + 16, &st);
+  if (!out) return st;
+  auto host = pinned_alloc((size_t)total + 16, &st);
+  if (!host) return st;
+  DFX_HIP(hipMemsetAsync(out.get(), 0, (size_t)total + 16, s));  // dictionary data pages are ORed into zeroes
+  DFX_HIP(launch_pqwd_encode(plan, (const uint32_t*)slot_of_row.get(), (const PqwdTile*)tiles.get(), d_pages, (uint8_t*)out.get(), total, ctrl, s));
+  DFX_HIP(hipMemcpyAsync((void*)hc, ctrl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (total) DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));  // the bodies
+  if (*hc != 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: the dictionary kernels disagree about a tile, or a tile would leave its page or its dictionary");
+  held_buffers_.push_back(host);
+  for (int k = 0; k < nc; ++k) {
+    if (states[cols[k]].mode != PQWD_MODE_DICT) continue;
+    for (int64_t p = 0; p < plan.base.n_pages; ++p) {
+      const PqwPage& g = pt[(int64_t)k * plan.base.n_pages + p];
+      const uint64_t body = (uint64_t)g.level_bytes + g.val_bytes;
+      if (g.base > total || body > total - g.base) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a page lies outside its launch's buffer");
+      HeldPage h;
+      h.num_values = std::min<int64_t>(opt_.page_rows, n - p * opt_.page_rows);
+      h.non_null = (int64_t)g.non_null;
+      h.body = (const uint8_t*)host.get() + g.base;
+      h.bytes = (size_t)body;
+      h.encoding = ENCODING_RLE_DICTIONARY;
+      held_[(size_t)cols[k]].push_back(h);
+      const uint32_t levels = g.kind & ((1u << kPqwdRunShift) - 1u);
+      if (levels == LEVELS_MIXED) ++counters().parquet_write_bitpacked_level_pages;
+      else if (levels != LEVELS_NONE) ++counters().parquet_write_rle_level_pages;
+      ++counters().parquet_write_dict_index_pages;
+      if (g.kind >> kPqwdRunShift == DICT_RUN_RLE) ++counters().parquet_write_dict_rle_index_pages;
+    }
+  }
   return Status::OK();
 }
 
-// the open row group goes to the file: per column [header][body] of every page, offsets recorded by the writer
+// one launch: the columns in dictionary mode first; then the others -- with those that have just fallen back -- as PLAIN pages
+Status ParquetSink::encode_rows(const DeviceBatch& b, int64_t r0, int64_t n) {
+  const int n_cols = (int)b.columns.size();
+  std::vector<int> cols;
+  for (int c = 0; c < n_cols; ++c)
+    if (dict_[(size_t)c].active) cols.push_back(c);
+  for (size_t c0 = 0; c0 < cols.size(); c0 += kPqwMaxCols) DFX_RETURN_IF_ERROR(encode_dict_columns(b, cols.data() + c0, (int)std::min<size_t>(kPqwMaxCols, cols.size() - c0), r0, n));
+  cols.clear();
+  for (int c = 0; c < n_cols; ++c)
+    if (!dict_[(size_t)c].active) cols.push_back(c);
+  for (size_t c0 = 0; c0 < cols.size(); c0 += kPqwMaxCols) DFX_RETURN_IF_ERROR(encode_columns(b, cols.data() + c0, (int)std::min<size_t>(kPqwMaxCols, cols.size() - c0), r0, n));
+  return Status::OK();
+}
+
+// a row group opens: under "dictionary" every non-Boolean column starts an empty dictionary -- its table {empty, none, unassigned}
+Status ParquetSink::open_group() {
+  if (opt_.dictionary <= 0) return Status::OK();
+  hipStream_t s = ctx().stream;
+  const SchemaInfo& sc = in_->schema();
+  Status st;
+  dict_slots_ = dict_table_slots((uint64_t)opt_.dictionary, (uint64_t)opt_.row_group_rows);
+  if (!dict_states_) {
+    dict_states_ = device_alloc(sizeof(PqwdState) * dict_.size(), &st);
+    if (!dict_states_) return st;
+  }
+  DFX_HIP(hipMemsetAsync(dict_states_.get(), 0, sizeof(PqwdState) * dict_.size(), s));
+  for (size_t c = 0; c < dict_.size(); ++c) {
+    DictColumn& dc = dict_[c];
+    if (!dictionary_dtype(sc.fields[c].dtype)) continue;
+    if (!dc.slots) {
+      dc.slots = device_alloc(sizeof(PqwdSlot) * (size_t)(dict_slots_ + 1), &st);  // (+ 1: the slot of the key that equals the empty word)
+      if (!dc.slots) return st;
+      if (sc.fields[c].dtype == DFX_UTF8) {
+        dc.entry_off = device_alloc(sizeof(uint32_t) * (size_t)dict_slots_, &st);
+        if (!dc.entry_off) return st;
+      }
+    }
+    DFX_HIP(hipMemsetAsync(dc.slots.get(), 0xFF, sizeof(PqwdSlot) * (size_t)(dict_slots_ + 1), s));
+    dc.active = true;
+    dc.launches = 0;
+    dc.entries = dc.body_bytes = 0;
+  }
+  return Status::OK();
+}
+
+// the open row group goes to the file: per column the dictionary page of a dictionary chunk, then [header][body] of every page,
+// offsets recorded by the writer
 Status ParquetSink::close_group() {
+  hipStream_t s = ctx().stream;
+  std::vector<std::shared_ptr<void>> bodies(dict_.size());
+  bool any = false;
+  for (size_t c = 0; c < dict_.size(); ++c) {
+    const DictColumn& dc = dict_[c];
+    if (dc.launches == 0 || dc.body_bytes == 0) continue;
+    Status st;
+    bodies[c] = pinned_alloc((size_t)dc.body_bytes, &st);
+    if (!bodies[c]) return st;
+    DFX_HIP(hipMemcpyAsync(bodies[c].get(), dc.body.get(), (size_t)dc.body_bytes, hipMemcpyDeviceToHost, s));
+    any = true;
+  }
+  if (any) DFX_HIP(hipStreamSynchronize(s));  // the dictionary bodies: once per row group
   writer_.begin_row_group();
   for (size_t c = 0; c < held_.size(); ++c) {
     writer_.begin_chunk(c);
+    if (dict_[c].launches > 0) {
+      if (!writer_.add_dictionary_page((int64_t)dict_[c].entries, bodies[c].get(), (size_t)dict_[c].body_bytes)) return io_error();
+      ++counters().parquet_write_dict_pages;
+      counters().parquet_write_dict_entries += (long long)dict_[c].entries;
+      dict_[c].launches = 0;
+    }
     for (const HeldPage& h : held_[c])
-      if (!writer_.add_page(h.num_values, h.non_null, h.body, h.bytes)) return io_error();
+      if (!writer_.add_page(h.num_values, h.non_null, h.body, h.bytes, h.encoding)) return io_error();
     held_[c].clear();
   }
   writer_.end_row_group(group_rows_);
@@ -222,6 +438,7 @@ Status ParquetSink::run(int64_t* rows, int64_t* bytes) {
   created_ = true;
   if (!writer_.begin()) return io_error();
   held_.assign(n_cols, std::vector<HeldPage>());
+  dict_.assign(n_cols, DictColumn());
   const int64_t per_launch = launch_rows(opt_.page_rows);
   int64_t n_rows = 0;
   for (;;) {
@@ -232,6 +449,7 @@ Status ParquetSink::run(int64_t* rows, int64_t* bytes) {
     if (b.columns.size() != n_cols) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: batch and schema disagree");
     for (int64_t r0 = 0; r0 < b.num_rows;) {
       const int64_t piece = piece_rows(group_rows_, b.num_rows - r0, opt_.row_group_rows);
+      if (group_rows_ == 0) DFX_RETURN_IF_ERROR(open_group());
       for (int64_t l0 = 0; l0 < piece; l0 += per_launch) DFX_RETURN_IF_ERROR(encode_rows(b, r0 + l0, std::min<int64_t>(per_launch, piece - l0)));
       r0 += piece;
       group_rows_ += piece;

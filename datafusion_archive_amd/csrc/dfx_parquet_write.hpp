@@ -9,7 +9,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include "dfx_parquet_enc.hpp"
+#include "dfx_parquet_dict_enc.hpp"
 
 namespace dfx {
 
@@ -37,5 +37,64 @@ hipError_t launch_pqw_measure(const DevPqwPlan& plan, pqw::PqwTile* tiles, hipSt
 hipError_t launch_pqw_scan(const DevPqwPlan& plan, pqw::PqwTile* tiles, pqw::PqwPage* pages, hipStream_t s);  // pages: n_cols * n_pages + 1
 hipError_t launch_pqw_encode(const DevPqwPlan& plan, const pqw::PqwTile* tiles, const pqw::PqwPage* pages, uint8_t* out, uint64_t out_bytes,
                              uint64_t* ctrl, hipStream_t s);
+
+hipError_t launch_pqw_bases(pqw::PqwPage* pages, int64_t n, hipStream_t s);  // the bases kernel alone (pages: n + 1)
+
+// ---- the "dictionary" option (dfx_k_parquet_write_dict.hip; the format and the decision: dfx_parquet_dict_enc.hpp) -------------------
+// One launch chain over the columns of a launch whose chunks are in dictionary mode:
+//   insert (a lane per valid row: the row's slot in its chunk's table) -> mark (a wave per tile: the rows that introduce an entry, the
+//   Utf8 compare against the slot's representative) -> decide (a workgroup per column: the launch's new entries and body bytes, the
+//   rule, the chunk's state) -> scan (a wave per page: the run kind and sizes into the PqwPage table) -> bases -> [host reads the page
+//   table and the states back, sizes the output buffer and the dictionary bodies] -> commit (a wave per tile: ids, the entries appended
+//   to the body) -> encode (a wave per tile: levels, width byte, run header, indices).
+// No lane waits for another lane's store inside a launch: what one kernel leaves for another is read by a later launch on the same
+// stream; inside a launch lanes meet only through agent-scope atomics (CAS on a key word, min on first_row, or on a flag or an output
+// word) whose returned value is all they use.
+constexpr uint64_t kPqwdEmpty = ~0ull;        // a key word no row has claimed; a row whose key IS this value uses the slot after the table
+constexpr uint32_t kPqwdNone = 0xFFFFFFFFu;   // id: unassigned; first_row: none yet; slot_of_row: null row, or no slot found
+constexpr uint32_t kPqwdMaxProbe = 1024;      // slots a row looks at before it gives up (the launch then falls back)
+struct PqwdSlot {      // 16 bytes; a chunk's table is memset to 0xFF when its row group opens: {empty, none, unassigned}
+  uint64_t key;        // fixed width: the stored bits; Utf8: the masked 64-bit hash of the bytes
+  uint32_t first_row;  // the launch-local row that introduces the entry: the least row of the launch that reached the slot
+  uint32_t id;         // assigned by the commit of the launch that introduced the entry
+};
+enum : uint32_t { PQWD_MODE_DICT = 0, PQWD_MODE_PLAIN = 1 };
+enum : uint32_t { PQWD_OVERFLOW = 1u, PQWD_COLLISION = 2u };  // a probe ran out or the claims exceed N - E; two Utf8 values share a hash
+struct PqwdState {     // per chunk, zeroed when the row group opens; written by decide, read back with the page table
+  uint64_t entries, body_bytes;  // E and B after the last launch held in dictionary mode
+  uint64_t entries_before, body_before;  // ... and before it: where commit appends
+  uint32_t mode;       // PQWD_MODE_*
+  uint32_t flags;      // PQWD_OVERFLOW / PQWD_COLLISION, raised by insert / mark of the launch that then fell back
+  uint32_t width;      // index width of the last launch held
+  uint32_t claimed;    // insert: key words claimed in the running launch; decide zeroes it
+};
+struct PqwdTile {      // per column and tile of a launch
+  uint32_t non_null, rank_base;    // mark / scan, as PqwTile
+  uint32_t entries, entry_base;    // mark: rows of the tile that introduce an entry; decide: ... of the launch's tiles before it
+  uint32_t min_slot, max_slot;     // mark: over the tile's valid rows (kPqwdNone / 0 without one)
+  uint64_t bytes, byte_base;       // mark / decide: dictionary body bytes of the introduced entries
+};
+// the index run's kind (pqw::DICT_RUN_*) rides in PqwPage::kind above the level kind
+constexpr uint32_t kPqwdRunShift = 8;
+struct DevPqwdCol {
+  PqwdSlot* slots;     // mask + 2 slots: the table, then the slot of the key that equals kPqwdEmpty
+  PqwdState* state;
+  uint8_t* body;       // the dictionary page's body: [0, body_cap)
+  uint32_t* entry_off; // Utf8: byte of every entry's length prefix in body, by id
+  uint64_t body_cap;
+  uint32_t mask;       // table slots - 1
+  uint32_t limit;      // N
+};
+struct DevPqwdPlan {
+  DevPqwPlan base;
+  DevPqwdCol dict[kPqwMaxCols];
+  uint64_t hash_mask;  // Utf8 hashes are cut to "dictionary_hash_bits" bits
+};
+static_assert(sizeof(DevPqwdPlan) <= 4096, "the plan is a kernel argument");
+
+// slot_of_row: n_cols * rows words; tiles: n_cols * n_tiles; pages: n_cols * n_pages + 1; ctrl as above
+hipError_t launch_pqwd_measure(const DevPqwdPlan& plan, uint32_t* slot_of_row, PqwdTile* tiles, pqw::PqwPage* pages, hipStream_t s);
+hipError_t launch_pqwd_encode(const DevPqwdPlan& plan, const uint32_t* slot_of_row, const PqwdTile* tiles, const pqw::PqwPage* pages, uint8_t* out,
+                              uint64_t out_bytes, uint64_t* ctrl, hipStream_t s);
 
 }  // namespace dfx

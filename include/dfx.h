@@ -394,8 +394,9 @@ int32_t dfx_csv_write(struct ArrowArrayStream* input, const char* filename, cons
  * nullability, nulls, values by bit pattern: NaN payloads, -0.0 and null Utf8 slots included), and so does
  * dfx_parquet_datasource_new.
  *   format    PAR1; a flat schema, one leaf per input column, in order, with the input's names; a field the input schema flags
- *             nullable is OPTIONAL, else REQUIRED.  Codec UNCOMPRESSED, data pages V1, encoding PLAIN, no dictionary pages, no page
- *             CRC, no page index; chunk statistics carry null_count only; created_by names the library
+ *             nullable is OPTIONAL, else REQUIRED.  Codec UNCOMPRESSED, data pages V1, encoding PLAIN (dictionary pages and
+ *             RLE_DICTIONARY data pages only under the "dictionary" option, below), no page CRC, no page index; chunk statistics
+ *             carry null_count only; created_by names the library
  *   types     Boolean -> BOOLEAN;  Int8 .. Int32, UInt8 .. UInt32 -> INT32 with Int(bits, signed) and the matching converted type,
  *             values sign / zero extended to 4 bytes;  Int64 -> INT64;  UInt64 -> INT64 with Int(64, false);  Float32 -> FLOAT;
  *             Float64 -> DOUBLE;  Utf8 -> BYTE_ARRAY annotated String / UTF8
@@ -405,8 +406,27 @@ int32_t dfx_csv_write(struct ArrowArrayStream* input, const char* filename, cons
  *   geometry  the input's rows are cut into row groups of exactly "row_group_rows" rows (the last shorter; a batch that crosses a
  *             boundary is split there); inside a group the rows of each batch are cut into pages of "page_rows" rows (the last
  *             shorter): a page never holds rows of two batches.  Zero rows: a valid file with the schema and no row group
- * `options`: "row_group_rows" (default 2^20, any value >= 1), "page_rows" (default 2^15; a multiple of 64, 64 .. 2^30); any other key
- * or value is DFX_GENERAL.  Errors: a column type outside Boolean .. Utf8 is DFX_NOT_IMPLEMENTED naming the column and the type,
+ *   dictionary  "dictionary" = N > 0: every non-Boolean column chunk (row group and column) starts dictionary-encoded, its
+ *             dictionary built on the device: keyed on the STORED bit pattern (fixed width: the widened value -- NaN payloads are
+ *             entries of their own, -0.0 and +0.0 are two; Utf8: the bytes; null slots contribute nothing), ids in order of first
+ *             occurrence in the chunk's row order.  The dictionary page is the chunk's first page (PageHeader type DICTIONARY_PAGE,
+ *             DictionaryPageHeader { num_values = entries, encoding PLAIN }; the entries in id order: stored width each, LE32 length +
+ *             bytes for Utf8; dictionary_page_offset set, data_page_offset the first data page, encodings PLAIN, RLE,
+ *             RLE_DICTIONARY, total sizes with the dictionary page).  A dictionary data page (V1, RLE_DICTIONARY): the level block
+ *             as above, one byte w, then ONE run over the page's nn non-null values: nothing when nn == 0; an RLE run when all its
+ *             indices are equal (varint(nn << 1), the index in ceil(w / 8) bytes); else one bit-packed run (varint(ceil(nn / 8) << 1
+ *             | 1), ceil(nn / 8) * w bytes, LSB first, padding bits zero).  w = max(1, bits(max(E, 1) - 1)), E the chunk's entries
+ *             after the launch that holds the page.  The unit of decision is the LAUNCH -- the rows of one batch inside one row
+ *             group, at most 2^20 of them (a whole number of pages; one page where page_rows is larger): a launch that would take the
+ *             dictionary beyond N entries, or its body to 2^31 - 1 bytes, turns the chunk PLAIN from that launch to its end (the
+ *             dictionary pages already held stay; a chunk that falls back in its first launch is byte for byte the chunk written
+ *             without the option).  A new row group starts every column with an empty dictionary.  Boolean columns stay PLAIN
+ * `options`: "row_group_rows" (default 2^20, any value >= 1), "page_rows" (default 2^15; a multiple of 64, 64 .. 2^30), "dictionary"
+ * (default 0: PLAIN pages only, files byte for byte what they are without the key; 1 .. 2^20: the most entries of a chunk's
+ * dictionary), "dictionary_hash_bits" (debug; 1 .. 64, default 64: the device's hash of a Utf8 value is cut to that many bits, so
+ * that a test can make two strings collide and see the chunk fall back to PLAIN; means nothing without "dictionary"); "dictionary" > 0
+ * takes "page_rows" of at most 2^20 (the dictionary kernels keep a word per row and column of a launch); any other key
+ * or value is DFX_GENERAL naming the key, before a device is asked for.  Errors: a column type outside Boolean .. Utf8 is DFX_NOT_IMPLEMENTED naming the column and the type,
  * before a file exists and before a device is asked for; no device is DFX_EXECUTION_ERROR (there is no host encoding path); a path
  * that cannot be created or written is DFX_IO_ERROR; a REQUIRED field whose batch arrives with nulls is DFX_EXECUTION_ERROR naming
  * the column; a page body of 2^31 - 1 bytes or more is DFX_EXECUTION_ERROR (the page header's sizes are i32).  The bytes go to
@@ -593,7 +613,12 @@ int32_t dfx_set_option(const char* key, int64_t value);
  *   "parquet_write_pages", "parquet_write_row_groups"   data pages / row groups written
  *   "parquet_write_bytes"         bytes of the files written
  *   "parquet_write_rle_level_pages", "parquet_write_bitpacked_level_pages"   pages of OPTIONAL columns whose definition levels are
- *                                 one RLE run (every row valid, or none) / one bit-packed run (valid and null rows) */
+ *                                 one RLE run (every row valid, or none) / one bit-packed run (valid and null rows)
+ *   "parquet_write_dict_pages", "parquet_write_dict_entries"   "dictionary" > 0 (tests/test_gpu_parquet_dict_write.py): dictionary
+ *                                 pages written / the entries they hold ("parquet_write_pages" keeps counting data pages only)
+ *   "parquet_write_dict_index_pages", "parquet_write_dict_rle_index_pages"   data pages of dictionary indices / of them, pages whose
+ *                                 indices are one RLE run (all equal)
+ *   "parquet_write_dict_fallback_chunks"   chunks that left dictionary mode for PLAIN, a fallback in the first launch included */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 

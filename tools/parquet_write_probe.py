@@ -5,26 +5,41 @@ Reports bytes of FILE per second
   (b) of the whole dfx_parquet_write call by wall clock (kernels, the page-table read-back, D2H into pinned buffers, fwrite),
   (c) of dfx_csv_write over the same table (bytes of text), and
   (d) of pyarrow.parquet.write_table(compression="NONE", use_dictionary=False) of the same table on the host.
+With `--dictionary N` it probes the "dictionary" option instead: the same two tables and a third whose Utf8 column draws from 10^3
+distinct strings, each written without the option and with dictionary = N -- file bytes, kernel time, the whole call, and the time the
+library's own Parquet source takes to scan each of the two files.
 Single runs on a shared machine: no threshold is derived from them and no test times anything.
-usage: parquet_write_probe.py [rows, default 2^24] [out=<directory>, default /dev/shm or the temp directory]"""
+With `--host-encoder EXE` (beside `--dictionary N`; needs no GPU) it writes the same three seeded tables with the sequential host encoder
+instead -- EXE is tests/native/parquet_dict_write_check.cpp built -- and prints the file sizes the device's files must have.
+usage: parquet_write_probe.py [rows, default 2^24] [out=<directory>, default /dev/shm or the temp directory] [--dictionary N [--host-encoder EXE]]"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pyarrow as pa
 import pyarrow.parquet as pq
 from datafusion_archive_amd import execution as ex
+dictionary = 0
+if "--dictionary" in sys.argv:
+    at = sys.argv.index("--dictionary")
+    dictionary = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+host_encoder = None
+if "--host-encoder" in sys.argv:
+    at = sys.argv.index("--host-encoder")
+    host_encoder = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
 rows = int(float(sys.argv[1])) if len(sys.argv) > 1 and "=" not in sys.argv[1] else 1 << 24
 out_dir = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
 for kv in sys.argv[1:]:
     if kv.startswith("out="): out_dir = kv[4:]
 out = os.path.join(out_dir, "dfx_parquet_write_probe.out")
 COUNTERS = ["parquet_write_pages", "parquet_write_row_groups", "parquet_write_rle_level_pages", "parquet_write_bitpacked_level_pages"]
-ex.init(0)
+if host_encoder is None: ex.init(0)
 
 
-def table(nullable):
+def table(nullable, distinct=4096):
     rng = np.random.default_rng(17)
-    names = np.array(["".join(chr(97 + int(c)) for c in rng.integers(0, 26, int(n))) for n in rng.integers(4, 21, 4096)])
+    names = np.array(["".join(chr(97 + int(c)) for c in rng.integers(0, 26, int(n))) for n in rng.integers(4, 21, distinct)])
     schema = pa.schema([pa.field("x", pa.float64(), nullable), pa.field("y", pa.float64(), nullable), pa.field("k", pa.int64(), nullable), pa.field("s", pa.string(), nullable)])
     pieces, piece = [], 1 << 22
     name_arr = pa.array(names, pa.string())
@@ -47,8 +62,59 @@ def timed(run, reps=3):
     return (time.perf_counter() - t0) / reps
 
 
+DICT_COUNTERS = ["parquet_write_dict_pages", "parquet_write_dict_entries", "parquet_write_dict_index_pages", "parquet_write_dict_rle_index_pages",
+                 "parquet_write_dict_fallback_chunks"]
+
+
+DICT_TABLES = (("REQUIRED", False, 4096), ("OPTIONAL, one null in eight", True, 4096), ("REQUIRED, Utf8 of 10^3 distinct strings", False, 1000))
+
+
+def host_sizes():
+    """the three tables through the sequential host encoder, in the batches the resident table hands out (scan(0): one batch per piece)"""
+    import json, subprocess
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import parquet_write_cases as W
+    for what, nullable, distinct in DICT_TABLES:
+        schema, pieces = table(nullable, distinct)
+        desc = out + ".desc"
+        with open(desc, "wb") as fh: fh.write(W.describe(schema, pieces))
+        print(f"host encoder ({what}): rows={rows}")
+        for n in (0, dictionary):
+            r = subprocess.run([host_encoder, "write", desc, out, str(n)], capture_output=True, text=True)
+            report = json.loads(r.stdout)
+            assert r.returncode == 0 and report["code"] == 0 and report["reader_code"] == 0 and report["mismatch"] == "", (r.returncode, r.stderr[-500:])
+            print(f"  options { {'dictionary': n} if n else 'none'}: file={report['bytes']} bytes")
+        os.remove(desc)
+
+
+def probe_dictionary():
+    for what, nullable, distinct in DICT_TABLES:
+        schema, pieces = table(nullable, distinct)
+        t = ex.DeviceTable.from_batches(schema, pieces)
+        del pieces
+        print(f"parquet write dictionary probe ({what}): rows={rows}")
+        for options in ({}, {"dictionary": dictionary}):
+            run = lambda: ex.write_parquet(t.scan(0), out, options)
+            wall = timed(run)
+            ex.profile_reset(); ex.profile_enable(True); ex.counter_reset()
+            _, nbytes = run()
+            ex.profile_enable(False)
+            prof = {p["kernel"]: p for p in ex.profile_snapshot()}["parquet_write"]
+            counters = {k: ex.counter_get(k) for k in COUNTERS + DICT_COUNTERS}
+            def scan():
+                for _ in ex.ParquetDataSource(out): pass
+            scan_wall = timed(scan)
+            print(f"  options {options or 'none'}: file={nbytes} bytes ({nbytes / rows:.1f} per row); kernels ({prof['launches']} tracked launches) {prof['total_ms']:.3f} ms; "
+                  f"whole call (mean of 3) {wall * 1e3:.1f} ms; scan of the file by the Parquet source (mean of 3) {scan_wall * 1e3:.1f} ms")
+            print(f"    counters: {counters}")
+        del t
+
+
 try:
     import pyarrow.compute  # noqa: F401
+    if dictionary > 0:
+        host_sizes() if host_encoder else probe_dictionary()
+        sys.exit(0)
     for nullable in (False, True):
         schema, pieces = table(nullable)
         t = ex.DeviceTable.from_batches(schema, pieces)
