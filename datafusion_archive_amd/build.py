@@ -30,12 +30,12 @@ def _pass1_units() -> List[str]:
 SOURCES = ["dfx_k_table1.hip", "dfx_k_table2.hip", "dfx_k_table3.hip", "dfx_k_table4.hip", "dfx_k_table8.hip", "dfx_k_core.hip", "dfx_k_filter.hip",
            "dfx_k_reduce.hip", "dfx_k_pass2.hip", "dfx_k_partition.hip"] + [f"dfx_k_partition_{u}.hip" for u in _pass1_units()] + [
            "dfx_k_fewgroup.hip", "dfx_k_distinct1.hip", "dfx_k_distinct2.hip", "dfx_k_distinct3.hip", "dfx_k_distinct4.hip",
-           "dfx_k_distinct8.hip", "dfx_k_csv.hip", "dfx_k_sort.hip", "dfx_k_dict.hip", "dfx_k_utf8pred.hip", "dfx_k_utf8agg.hip", "dfx_k_csvwrite.hip", "dfx_k_parquet.hip", "dfx_k_parquet_write.hip", "dfx_k_parquet_write_dict.hip", "dfx_launch.cpp", "dfx_host.cpp", "dfx_expr.cpp", "dfx_expr_program.cpp", "dfx_expr_utf8.cpp", "dfx_relation.cpp", "dfx_host_stream.cpp", "dfx_export.cpp",
+           "dfx_k_distinct8.hip", "dfx_k_csv.hip", "dfx_k_sort.hip", "dfx_k_dict.hip", "dfx_k_utf8pred.hip", "dfx_k_utf8agg.hip", "dfx_k_csvwrite.hip", "dfx_k_parquet.hip", "dfx_k_parquet_write.hip", "dfx_k_parquet_write_dict.hip", "dfx_k_parquet_write_lz4.hip", "dfx_launch.cpp", "dfx_host.cpp", "dfx_expr.cpp", "dfx_expr_program.cpp", "dfx_expr_utf8.cpp", "dfx_relation.cpp", "dfx_host_stream.cpp", "dfx_export.cpp",
            "dfx_filter.cpp", "dfx_project.cpp", "dfx_aggregate.cpp", "dfx_aggregate_strategy.cpp",
            "dfx_aggregate_table.cpp", "dfx_aggregate_ctrl.cpp", "dfx_aggregate_shadow.cpp", "dfx_aggregate_launch.cpp", "dfx_aggregate_emit.cpp", "dfx_aggregate_partial.cpp", "dfx_utf8_dict.cpp",
            "dfx_gather.cpp", "dfx_table.cpp", "dfx_options.cpp", "dfx_csv.cpp", "dfx_sort.cpp", "dfx_comm.cpp", "dfx_exchange.cpp", "dfx_distinct.cpp", "dfx_distinct_sets.cpp", "dfx_distinct_emit.cpp",
            "dfx_csv_write.cpp", "dfx_parquet.cpp", "dfx_parquet_write.cpp"]
-HEADERS = ["dfx_device.hpp", "dfx_sigs.hpp", "dfx_row_source.hpp", "dfx_scan_plan.hpp", "dfx_numparse.hpp", "dfx_utf8_match.hpp", "dfx_pow5_table.hpp", "dfx_numfmt.hpp", "dfx_pow10_table.hpp", "dfx_csvwrite.hpp", "dfx_csv_walk.hpp", "dfx_parquet_rle.hpp", "dfx_parquet_lz4.hpp", "dfx_parquet_meta.hpp", "dfx_parquet_thrift_write.hpp", "dfx_parquet_enc.hpp", "dfx_parquet_dict_enc.hpp", "dfx_parquet_write.hpp", "dfx_k_parquet_write_inl.hpp", "dfx_scan_rules.hpp", "dfx_kernels.hpp", "dfx_k_base_inl.hpp", "dfx_k_interp_inl.hpp", "dfx_k_policy_inl.hpp", "dfx_k_plan_policy_inl.hpp", "dfx_k_acc_inl.hpp", "dfx_k_table_inl.hpp", "dfx_k_partition_inl.hpp", "dfx_k_partition_ws_inl.hpp", "dfx_k_distinct_inl.hpp", "dfx_launch.hpp",
+HEADERS = ["dfx_device.hpp", "dfx_sigs.hpp", "dfx_row_source.hpp", "dfx_scan_plan.hpp", "dfx_numparse.hpp", "dfx_utf8_match.hpp", "dfx_pow5_table.hpp", "dfx_numfmt.hpp", "dfx_pow10_table.hpp", "dfx_csvwrite.hpp", "dfx_csv_walk.hpp", "dfx_parquet_rle.hpp", "dfx_parquet_lz4.hpp", "dfx_parquet_meta.hpp", "dfx_parquet_thrift_write.hpp", "dfx_parquet_enc.hpp", "dfx_parquet_dict_enc.hpp", "dfx_parquet_lz4_enc.hpp", "dfx_parquet_write.hpp", "dfx_k_parquet_write_inl.hpp", "dfx_scan_rules.hpp", "dfx_kernels.hpp", "dfx_k_base_inl.hpp", "dfx_k_interp_inl.hpp", "dfx_k_policy_inl.hpp", "dfx_k_plan_policy_inl.hpp", "dfx_k_acc_inl.hpp", "dfx_k_table_inl.hpp", "dfx_k_partition_inl.hpp", "dfx_k_partition_ws_inl.hpp", "dfx_k_distinct_inl.hpp", "dfx_launch.hpp",
            "dfx_host.hpp", "dfx_pass1_units.hpp", "dfx_pass1_layout.hpp", "dfx_agg_rules.hpp", "dfx_pass2_forms.hpp", "dfx_key_shadow.hpp", "dfx_value_shadow.hpp", "dfx_routed_shadow.hpp", "dfx_relation.hpp", "dfx_gather.hpp", "dfx_utf8_dict.hpp", "dfx_exchange_plan.hpp", "dfx_comm.hpp", "dfx_aggregate_impl.hpp", "dfx_distinct_impl.hpp", "../../include/dfx.h"]
 
 # -ffp-contract=off : the reference never fuses a*b+c; projections must be bit-exact

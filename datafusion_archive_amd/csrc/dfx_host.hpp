@@ -205,6 +205,10 @@ struct Counters {  // every field a long long with its name in kCounterNames (df
   long long parquet_write_dict_index_pages = 0;        // ... data pages of dictionary indices (counted in parquet_write_pages as well)
   long long parquet_write_dict_rle_index_pages = 0;    // ... of them, pages whose indices are one RLE run (all equal)
   long long parquet_write_dict_fallback_chunks = 0;    // ... chunks that left dictionary mode for PLAIN, a fallback in the first launch included
+  long long parquet_write_lz4_pages = 0;               // "compression" = 7: page bodies packed into LZ4 blocks on the device, dictionary pages included
+  long long parquet_write_lz4_bytes_in = 0;            // ... bytes of those bodies
+  long long parquet_write_lz4_bytes_out = 0;           // ... bytes of their blocks
+  long long parquet_write_lz4_sequences = 0;           // ... sequences of their blocks
 };
 struct ScopedUs {  // adds the scope's wall time to a counter
   long long* acc;

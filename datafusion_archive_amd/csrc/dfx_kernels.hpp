@@ -42,6 +42,7 @@ enum KernelId : int {
   KID_PARQUET,
   KID_PARQUET_INFLATE,
   KID_PARQUET_WRITE,
+  KID_PARQUET_WRITE_LZ4,
   KID_COUNT_
 };
 const char* kernel_name(int kid);

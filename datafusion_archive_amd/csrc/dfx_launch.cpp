@@ -10,7 +10,7 @@ namespace dfx {
 static const char* kKernelNames[KID_COUNT_] = {
     "predicate_mask", "compact", "project", "reduce_all", "hash_agg", "merge_rows", "rehash",
     "emit_mask", "finalize", "scan", "synth", "fill", "gather_utf8", "partial", "partition", "partition_agg", "csv", "sort",
-    "distinct_insert", "distinct_count", "utf8_pred", "utf8_extrema", "csv_write", "parquet", "parquet_inflate", "parquet_write"};
+    "distinct_insert", "distinct_count", "utf8_pred", "utf8_extrema", "csv_write", "parquet", "parquet_inflate", "parquet_write", "parquet_write_lz4"};
 const char* kernel_name(int kid) { return (kid >= 0 && kid < KID_COUNT_) ? kKernelNames[kid] : "?"; }
 
 namespace {

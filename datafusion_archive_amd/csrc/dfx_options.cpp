@@ -147,6 +147,10 @@ constexpr CounterName kCounterNames[] = {
     {"parquet_write_dict_index_pages",      &Counters::parquet_write_dict_index_pages},
     {"parquet_write_dict_rle_index_pages",  &Counters::parquet_write_dict_rle_index_pages},
     {"parquet_write_dict_fallback_chunks",  &Counters::parquet_write_dict_fallback_chunks},
+    {"parquet_write_lz4_pages",             &Counters::parquet_write_lz4_pages},
+    {"parquet_write_lz4_bytes_in",          &Counters::parquet_write_lz4_bytes_in},
+    {"parquet_write_lz4_bytes_out",         &Counters::parquet_write_lz4_bytes_out},
+    {"parquet_write_lz4_sequences",         &Counters::parquet_write_lz4_sequences},
     {"xchg_calls",                          &Counters::xchg_calls},
     {"xchg_local_us",                       &Counters::xchg_local_us},
     {"xchg_wait_peers_us",                  &Counters::xchg_wait_peers_us},

@@ -280,7 +280,8 @@ inline const char* created_by() { return "datafusion_archive_amd dfx_parquet_wri
 class FileWriter {
  public:
   typedef bool (*Put)(void* ctx, const void* p, size_t n);
-  FileWriter(std::vector<ColumnSpec> cols, Put put, void* ctx) : cols_(std::move(cols)), put_(put), ctx_(ctx) {}
+  // codec: the Parquet codec id of every chunk (0 UNCOMPRESSED; 7 LZ4_RAW: every body handed in is one raw LZ4 block)
+  FileWriter(std::vector<ColumnSpec> cols, Put put, void* ctx, int codec = 0) : cols_(std::move(cols)), put_(put), ctx_(ctx), codec_(codec) {}
   bool begin() { return emit("PAR1", 4); }
   void begin_row_group() { groups_.emplace_back(); }
   void begin_chunk(size_t c) {
@@ -289,23 +290,28 @@ class FileWriter {
     k.optional = cols_[c].nullable;
     k.name = cols_[c].name;
     k.data_page_offset = (int64_t)bytes_;
+    k.codec = codec_;
+    if (codec_ != 0) k.total_uncompressed_size = 0;
     groups_.back().chunks.push_back(k);
   }
-  // the chunk's first page: the PLAIN values of its dictionary, in id order (before any add_page of the chunk)
-  bool add_dictionary_page(int64_t entries, const void* body, size_t body_bytes) {
+  // the chunk's first page: the PLAIN values of its dictionary, in id order (before any add_page of the chunk).
+  // uncompressed_bytes (here and in add_page): of what a compressed body inflates to; below 0: body_bytes, an UNCOMPRESSED chunk
+  bool add_dictionary_page(int64_t entries, const void* body, size_t body_bytes, int64_t uncompressed_bytes = -1) {
     header_.clear();
-    write_dictionary_page_header((int32_t)body_bytes, (int32_t)entries, &header_);
+    write_dictionary_page_header((int32_t)body_bytes, (int32_t)entries, &header_, (int32_t)uncompressed_bytes);
     ChunkInfo& k = groups_.back().chunks.back();
+    if (k.total_uncompressed_size >= 0) k.total_uncompressed_size += (int64_t)header_.size() + (uncompressed_bytes < 0 ? (int64_t)body_bytes : uncompressed_bytes);
     k.has_dictionary = true;
     k.dictionary_page_offset = (int64_t)bytes_;
     k.total_size += (int64_t)(header_.size() + body_bytes);
     k.data_page_offset = (int64_t)(bytes_ + header_.size() + body_bytes);
     return emit(header_.data(), header_.size()) && emit(body, body_bytes);
   }
-  bool add_page(int64_t num_values, int64_t non_null, const void* body, size_t body_bytes, int encoding = ENCODING_PLAIN) {
+  bool add_page(int64_t num_values, int64_t non_null, const void* body, size_t body_bytes, int encoding = ENCODING_PLAIN, int64_t uncompressed_bytes = -1) {
     header_.clear();
-    write_page_header((int32_t)body_bytes, (int32_t)num_values, &header_, encoding);
+    write_page_header((int32_t)body_bytes, (int32_t)num_values, &header_, encoding, (int32_t)uncompressed_bytes);
     ChunkInfo& k = groups_.back().chunks.back();
+    if (k.total_uncompressed_size >= 0) k.total_uncompressed_size += (int64_t)header_.size() + (uncompressed_bytes < 0 ? (int64_t)body_bytes : uncompressed_bytes);
     k.num_values += num_values;
     k.null_count += num_values - non_null;
     k.total_size += (int64_t)(header_.size() + body_bytes);
@@ -339,6 +345,7 @@ class FileWriter {
   std::vector<ColumnSpec> cols_;
   Put put_;
   void* ctx_;
+  int codec_ = 0;
   std::vector<RowGroupInfo> groups_;
   std::vector<uint8_t> header_;
   uint64_t bytes_ = 0;

@@ -107,13 +107,14 @@ struct LeafSchema {
 };
 
 // PageHeader { 1 type = DATA_PAGE, 2 uncompressed_page_size, 3 compressed_page_size, 5 DataPageHeader { 1 num_values, 2 encoding = PLAIN,
-// 3 definition_level_encoding = RLE, 4 repetition_level_encoding = RLE } }: a V1 data page of an UNCOMPRESSED chunk, no CRC, no statistics;
-// encoding: PLAIN, or RLE_DICTIONARY for a page of dictionary indices
-inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out, int encoding = ENCODING_PLAIN) {
+// 3 definition_level_encoding = RLE, 4 repetition_level_encoding = RLE } }: a V1 data page, no CRC, no statistics;
+// encoding: PLAIN, or RLE_DICTIONARY for a page of dictionary indices; body_bytes: of the body as the file holds it;
+// uncompressed_bytes: of what it inflates to in a compressed chunk (below 0: the same, an UNCOMPRESSED chunk)
+inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out, int encoding = ENCODING_PLAIN, int32_t uncompressed_bytes = -1) {
   ThriftWriter t(out);
   t.begin_struct(0);
   t.i32(1, 0);
-  t.i32(2, body_bytes);
+  t.i32(2, uncompressed_bytes < 0 ? body_bytes : uncompressed_bytes);
   t.i32(3, body_bytes);
   t.begin_struct(5);
   t.i32(1, num_values);
@@ -125,11 +126,11 @@ inline void write_page_header(int32_t body_bytes, int32_t num_values, std::vecto
 }
 // PageHeader { 1 type = DICTIONARY_PAGE, 2 uncompressed_page_size, 3 compressed_page_size, 7 DictionaryPageHeader { 1 num_values,
 // 2 encoding = PLAIN } }: the first page of a dictionary-encoded chunk
-inline void write_dictionary_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out) {
+inline void write_dictionary_page_header(int32_t body_bytes, int32_t num_values, std::vector<uint8_t>* out, int32_t uncompressed_bytes = -1) {
   ThriftWriter t(out);
   t.begin_struct(0);
   t.i32(1, 2);
-  t.i32(2, body_bytes);
+  t.i32(2, uncompressed_bytes < 0 ? body_bytes : uncompressed_bytes);
   t.i32(3, body_bytes);
   t.begin_struct(7);
   t.i32(1, num_values);
@@ -168,12 +169,14 @@ struct ChunkInfo {  // one column chunk of a row group, as the footer records it
   bool optional = true;  // encodings: PLAIN, and RLE for the definition levels of an OPTIONAL column
   std::string name;
   int64_t num_values = 0, null_count = 0;
-  int64_t total_size = 0;  // headers + bodies of its pages (UNCOMPRESSED: both sizes)
+  int64_t total_size = 0;  // headers + bodies of its pages as the file holds them (UNCOMPRESSED: both sizes)
+  int codec = 0;           // the Parquet codec id of its pages: 0 UNCOMPRESSED, 7 LZ4_RAW
+  int64_t total_uncompressed_size = -1;  // headers + what the bodies inflate to (below 0: total_size, an UNCOMPRESSED chunk)
   int64_t data_page_offset = 0;
   bool has_dictionary = false;  // the chunk starts with a dictionary page: encodings PLAIN, RLE, RLE_DICTIONARY; total_size counts it
   int64_t dictionary_page_offset = 0;
 };
-// ColumnChunk { 2 file_offset, 3 ColumnMetaData { 1 type, 2 encodings, 3 path_in_schema, 4 codec = UNCOMPRESSED, 5 num_values,
+// ColumnChunk { 2 file_offset, 3 ColumnMetaData { 1 type, 2 encodings, 3 path_in_schema, 4 codec, 5 num_values,
 // 6 total_uncompressed_size, 7 total_compressed_size, 9 data_page_offset, 11 dictionary_page_offset (a chunk with a dictionary page),
 // 12 Statistics { 3 null_count } } }
 inline void write_column_chunk(ThriftWriter& t, const ChunkInfo& c) {
@@ -187,9 +190,9 @@ inline void write_column_chunk(ThriftWriter& t, const ChunkInfo& c) {
   if (c.has_dictionary) t.zigzag(ENCODING_RLE_DICTIONARY);
   t.list(3, TW_BINARY, 1);
   t.binary_value(c.name);
-  t.i32(4, 0);
+  t.i32(4, c.codec);
   t.i64(5, c.num_values);
-  t.i64(6, c.total_size);
+  t.i64(6, c.total_uncompressed_size < 0 ? c.total_size : c.total_uncompressed_size);
   t.i64(7, c.total_size);
   t.i64(9, c.data_page_offset);
   if (c.has_dictionary) t.i64(11, c.dictionary_page_offset);
@@ -210,7 +213,7 @@ inline void write_row_group(ThriftWriter& t, const RowGroupInfo& g) {
   int64_t total = 0;
   for (const ChunkInfo& c : g.chunks) {
     write_column_chunk(t, c);
-    total += c.total_size;
+    total += c.total_uncompressed_size < 0 ? c.total_size : c.total_uncompressed_size;  // (of the uncompressed column data)
   }
   t.i64(2, total);
   t.i64(3, g.num_rows);

@@ -18,6 +18,12 @@
 // that launch pays the ordinary chain's two synchronisations on top -- once in a chunk's life, which for a column that never fits its
 // dictionary is once per row group.  The dictionary bodies stay on the
 // device until the group closes: one copy and one synchronisation more per row group.  With the option at 0 none of this runs.
+//
+// Under "compression" = 7 (LZ4_RAW; dfx_parquet_lz4_enc.hpp has the block rule, dfx_k_parquet_write_lz4.hip the kernels) every body is
+// packed into one raw LZ4 block before it leaves the device: pack_bodies, called by both chains after their encode kernel and by
+// close_group for the dictionary bodies.  Only the blocks are copied into pinned memory: the open row group holds its COMPRESSED
+// bytes.  A chain pays one synchronisation more (the table of block sizes, by which the packed buffer is sized); close_group's shares
+// the one the dictionary copy has.  With the option at 0 none of this runs.
 #include <errno.h>
 #include <stdio.h>
 #include <string.h>
@@ -38,7 +44,14 @@ struct PqwOptions {
   int64_t page_rows = kDefaultPageRows;
   int64_t dictionary = 0;             // N: the most entries of a chunk's dictionary; 0: PLAIN pages only
   int64_t dictionary_hash_bits = 64;  // (debug) the Utf8 hash is cut to this many bits, so that a test can make strings collide
+  int64_t compression = kCodecUncompressed;  // the Parquet codec id of every chunk: 0, or 7 (LZ4_RAW)
 };
+
+// what the refusal of a codec id calls it (parquet.thrift's CompressionCodec)
+const char* other_codec_name(int64_t v) {
+  static const char* const names[] = {"UNCOMPRESSED", "SNAPPY", "GZIP", "LZO", "BROTLI", "LZ4", "ZSTD", "LZ4_RAW"};
+  return v >= 0 && v < 8 ? names[v] : "such a codec";
+}
 
 Status parse_options(const dfx_option* options, int32_t n_options, PqwOptions* o) {
   for (int32_t i = 0; i < n_options; ++i) {
@@ -56,6 +69,9 @@ Status parse_options(const dfx_option* options, int32_t n_options, PqwOptions* o
     } else if (!strcmp(key, "dictionary_hash_bits")) {
       if (!dictionary_hash_bits_ok(v)) return Status::Err(DFX_GENERAL, strfmt("dictionary_hash_bits = %lld: 1 to 64", (long long)v));
       o->dictionary_hash_bits = v;
+    } else if (!strcmp(key, "compression")) {
+      if (!compression_ok(v)) return Status::Err(DFX_GENERAL, strfmt("compression = %lld: 0 (UNCOMPRESSED) or 7 (LZ4_RAW); %s is not written", (long long)v, other_codec_name(v)));
+      o->compression = v;
     } else {
       return Status::Err(DFX_GENERAL, std::string("unknown option ") + key);
     }
@@ -77,7 +93,7 @@ Status judge_schema(const SchemaInfo& sc) {
 class ParquetSink {
  public:
   ParquetSink(std::unique_ptr<Relation> in, std::string filename, const PqwOptions& opt)
-      : in_(std::move(in)), final_(std::move(filename)), tmp_(final_ + ".dfx-partial"), opt_(opt), writer_(specs(in_->schema()), &ParquetSink::put, this) {}
+      : in_(std::move(in)), final_(std::move(filename)), tmp_(final_ + ".dfx-partial"), opt_(opt), writer_(specs(in_->schema()), &ParquetSink::put, this, (int)opt.compression) {}
   ~ParquetSink() {
     if (fp_) fclose(fp_);
     if (fp_ || created_) remove(tmp_.c_str());
@@ -90,6 +106,16 @@ class ParquetSink {
     const uint8_t* body;  // in one of held_buffers_
     size_t bytes;
     int encoding;  // ENCODING_PLAIN / ENCODING_RLE_DICTIONARY
+    int64_t uncompressed = -1;  // "compression": bytes of the body that `body` is the block of; below 0: `bytes`
+  };
+  struct PackedBodies {  // what pack_bodies leaves; to be read after the caller's next synchronisation, through check_packed
+    std::shared_ptr<void> host;                  // pinned: the blocks, each at its base
+    std::shared_ptr<void> table;                 // pinned: PqwLz4Out per body (already read back), then the control word
+    std::vector<std::shared_ptr<void>> device;   // what the kernels in flight read and write
+    std::vector<PqwLz4In> in;
+    const PqwLz4Out* out = nullptr;
+    const uint64_t* ctrl = nullptr;
+    const uint8_t* block(size_t i) const { return (const uint8_t*)host.get() + out[i].base; }
   };
   struct DictColumn {  // a column's chunk of the open row group under the "dictionary" option
     bool active = false;  // in dictionary mode (never: Boolean columns, the option at 0)
@@ -119,6 +145,9 @@ class ParquetSink {
   Status encode_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n);
   Status encode_dict_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n);
   Status plan_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n, DevPqwPlan* plan, bool* any_boolean);
+  Status pack_bodies(std::vector<PqwLz4In> in, PackedBodies* pk);
+  Status check_packed(const PackedBodies& pk);
+  bool lz4() const { return opt_.compression == kCodecLz4Raw; }
   Status check_pages(const PqwPage* pt, const DevPqwPlan& plan, int k, int col, int64_t n);
   Status open_group();
   Status close_group();
@@ -187,6 +216,73 @@ Status ParquetSink::check_pages(const PqwPage* pt, const DevPqwPlan& plan, int k
   return Status::OK();
 }
 
+// "compression" = 7: the bodies in[] (on the device, written by launches already on the stream) packed into raw LZ4 blocks, the blocks
+// copied into a pinned buffer sized by their total.  One synchronisation inside (the table of sizes); the copy of the blocks and of the
+// control word is left in flight: the caller synchronises and then asks check_packed.
+Status ParquetSink::pack_bodies(std::vector<PqwLz4In> in, PackedBodies* pk) {
+  hipStream_t s = ctx().stream;
+  Status st;
+  const size_t n = in.size();
+  if (n == 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: no body to pack");  // (the kernels would leave the table unwritten)
+  uint64_t slots_bytes = 0;
+  for (PqwLz4In& e : in) {
+    if (!lz4_body_fits(e.len))
+      return Status::Err(DFX_EXECUTION_ERROR, strfmt("Parquet writer: the LZ4 block of a page of %llu bytes may take 2^31 bytes or more; a page header holds sizes below 2^31 (smaller page_rows)",
+                                                     (unsigned long long)e.len));
+    e.slot_off = slots_bytes;
+    e.pad = 0;
+    slots_bytes += (lz4_bound(e.len) + 7ull) & ~7ull;
+  }
+  const size_t out_bytes = sizeof(PqwLz4Out) * (n + 1) + sizeof(uint64_t);
+  auto h_in = pinned_alloc(sizeof(PqwLz4In) * n + 16, &st);
+  if (!h_in) return st;
+  auto d_in = device_alloc(sizeof(PqwLz4In) * n + 16, &st);
+  if (!d_in) return st;
+  auto slots = device_alloc((size_t)slots_bytes + 16, &st);
+  if (!slots) return st;
+  auto d_out = device_alloc(out_bytes, &st);
+  if (!d_out) return st;
+  pk->table = pinned_alloc(out_bytes, &st);
+  if (!pk->table) return st;
+  memcpy(h_in.get(), in.data(), sizeof(PqwLz4In) * n);
+  PqwLz4Out* d_table = (PqwLz4Out*)d_out.get();
+  uint64_t* d_ctrl = (uint64_t*)(d_table + n + 1);
+  pk->out = (const PqwLz4Out*)pk->table.get();
+  pk->ctrl = (const uint64_t*)(pk->out + n + 1);
+  pk->device = {h_in, d_in, slots, d_out};
+  DFX_HIP(hipMemsetAsync(d_ctrl, 0, sizeof(uint64_t), s));
+  DFX_HIP(hipMemcpyAsync(d_in.get(), h_in.get(), sizeof(PqwLz4In) * n, hipMemcpyHostToDevice, s));
+  DFX_HIP(launch_pqw_lz4((const PqwLz4In*)d_in.get(), (int64_t)n, (uint8_t*)slots.get(), slots_bytes, d_table, d_ctrl, s));
+  DFX_HIP(hipMemcpyAsync(pk->table.get(), d_table, sizeof(PqwLz4Out) * (n + 1), hipMemcpyDeviceToHost, s));
+  DFX_HIP(hipStreamSynchronize(s));  // the table of block sizes: the option's one synchronisation more
+  const uint64_t total = pk->out[n].base;
+  for (size_t i = 0; i < n; ++i)
+    if ((uint64_t)pk->out[i].bytes > lz4_bound(in[i].len) || pk->out[i].base > total || (uint64_t)pk->out[i].bytes > total - pk->out[i].base)
+      return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: an LZ4 block is larger than its bound or lies outside the packed buffer");
+  auto packed = device_alloc((size_t)total + 16, &st);
+  if (!packed) return st;
+  pk->host = pinned_alloc((size_t)total + 16, &st);
+  if (!pk->host) return st;
+  pk->device.push_back(packed);
+  DFX_HIP(launch_pqw_lz4_compact((const PqwLz4In*)d_in.get(), d_table, (int64_t)n, (const uint8_t*)slots.get(), slots_bytes, (uint8_t*)packed.get(), total, d_ctrl, s));
+  DFX_HIP(hipMemcpyAsync((void*)pk->ctrl, d_ctrl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (total) DFX_HIP(hipMemcpyAsync(pk->host.get(), packed.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  pk->in = std::move(in);
+  return Status::OK();
+}
+
+// after the synchronisation that follows pack_bodies: the guard's verdict, and the counters
+Status ParquetSink::check_packed(const PackedBodies& pk) {
+  if (*pk.ctrl != 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: an LZ4 sequence would leave its block's slot, or a block its buffer");
+  for (size_t i = 0; i < pk.in.size(); ++i) {
+    ++counters().parquet_write_lz4_pages;
+    counters().parquet_write_lz4_bytes_in += (long long)pk.in[i].len;
+    counters().parquet_write_lz4_bytes_out += (long long)pk.out[i].bytes;
+    counters().parquet_write_lz4_sequences += (long long)pk.out[i].sequences;
+  }
+  return Status::OK();
+}
+
 // one launch chain of PLAIN pages over rows [r0, r0 + n) of the nc columns cols[] of the batch
 Status ParquetSink::encode_columns(const DeviceBatch& b, const int* cols, int nc, int64_t r0, int64_t n) {
   hipStream_t s = ctx().stream;
@@ -213,15 +309,31 @@ Status ParquetSink::encode_columns(const DeviceBatch& b, const int* cols, int nc
   const uint64_t total = pt[n_pages].base;
   auto out = device_alloc((size_t)total + 16, &st);
   if (!out) return st;
-  auto host = pinned_alloc((size_t)total + 16, &st);
-  if (!host) return st;
+  std::shared_ptr<void> host;
+  if (!lz4()) {
+    host = pinned_alloc((size_t)total + 16, &st);
+    if (!host) return st;
+  }
   if (any_boolean) DFX_HIP(hipMemsetAsync(out.get(), 0, (size_t)total + 16, s));  // Boolean pages are ORed into zeroes
   DFX_HIP(launch_pqw_encode(plan, (const PqwTile*)tiles.get(), d_pages, (uint8_t*)out.get(), total, ctrl, s));
   const uint64_t* hc = (const uint64_t*)((const PqwPage*)table.get() + n_pages + 1);
   DFX_HIP(hipMemcpyAsync((void*)hc, ctrl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (total) DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  PackedBodies pk;
+  if (lz4()) {
+    std::vector<PqwLz4In> in;
+    for (int64_t i = 0; i < n_pages; ++i) {
+      const uint64_t body = (uint64_t)pt[i].level_bytes + pt[i].val_bytes;
+      if (pt[i].base > total || body > total - pt[i].base) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a page lies outside its launch's buffer");
+      in.push_back(PqwLz4In{(const uint8_t*)out.get() + pt[i].base, 0, (uint32_t)body, 0});
+    }
+    DFX_RETURN_IF_ERROR(pack_bodies(std::move(in), &pk));
+    host = pk.host;
+  } else if (total) {
+    DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  }
   DFX_HIP(hipStreamSynchronize(s));  // the bodies
   if (*hc != 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: the measure and encode kernels disagree about a tile, or a tile would leave its page");
+  if (lz4()) DFX_RETURN_IF_ERROR(check_packed(pk));
   held_buffers_.push_back(host);
   for (int k = 0; k < nc; ++k)
     for (int64_t p = 0; p < plan.n_pages; ++p) {
@@ -233,6 +345,12 @@ Status ParquetSink::encode_columns(const DeviceBatch& b, const int* cols, int nc
       h.non_null = (int64_t)g.non_null;
       h.body = (const uint8_t*)host.get() + g.base;
       h.bytes = (size_t)body;
+      if (lz4()) {
+        const size_t i = (size_t)(k * plan.n_pages + p);
+        h.body = pk.block(i);
+        h.bytes = (size_t)pk.out[i].bytes;
+        h.uncompressed = (int64_t)body;
+      }
       h.encoding = ENCODING_PLAIN;
       held_[(size_t)cols[k]].push_back(h);
       if (g.kind == LEVELS_MIXED) ++counters().parquet_write_bitpacked_level_pages;
@@ -319,14 +437,33 @@ Status ParquetSink::encode_dict_columns(const DeviceBatch& b, const int* cols, i
   const uint64_t total = pt[n_pages].base;
   auto out = device_alloc((size_t)total + 16, &st);
   if (!out) return st;
-  auto host = pinned_alloc((size_t)total + 16, &st);
-  if (!host) return st;
+  std::shared_ptr<void> host;
+  if (!lz4()) {
+    host = pinned_alloc((size_t)total + 16, &st);
+    if (!host) return st;
+  }
   DFX_HIP(hipMemsetAsync(out.get(), 0, (size_t)total + 16, s));  // dictionary data pages are ORed into zeroes
   DFX_HIP(launch_pqwd_encode(plan, (const uint32_t*)slot_of_row.get(), (const PqwdTile*)tiles.get(), d_pages, (uint8_t*)out.get(), total, ctrl, s));
   DFX_HIP(hipMemcpyAsync((void*)hc, ctrl, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (total) DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  PackedBodies pk;
+  std::vector<int64_t> block_of((size_t)n_pages, -1);  // a page's entry in pk: the pages of the columns that stayed
+  if (lz4()) {
+    std::vector<PqwLz4In> in;
+    for (int64_t i = 0; i < n_pages; ++i) {
+      if (states[cols[i / plan.base.n_pages]].mode != PQWD_MODE_DICT) continue;
+      const uint64_t body = (uint64_t)pt[i].level_bytes + pt[i].val_bytes;
+      if (pt[i].base > total || body > total - pt[i].base) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: a page lies outside its launch's buffer");
+      block_of[(size_t)i] = (int64_t)in.size();
+      in.push_back(PqwLz4In{(const uint8_t*)out.get() + pt[i].base, 0, (uint32_t)body, 0});
+    }
+    DFX_RETURN_IF_ERROR(pack_bodies(std::move(in), &pk));
+    host = pk.host;
+  } else if (total) {
+    DFX_HIP(hipMemcpyAsync(host.get(), out.get(), (size_t)total, hipMemcpyDeviceToHost, s));
+  }
   DFX_HIP(hipStreamSynchronize(s));  // the bodies
   if (*hc != 0) return Status::Err(DFX_INTERNAL_ERROR, "Parquet writer: the dictionary kernels disagree about a tile, or a tile would leave its page or its dictionary");
+  if (lz4()) DFX_RETURN_IF_ERROR(check_packed(pk));
   held_buffers_.push_back(host);
   for (int k = 0; k < nc; ++k) {
     if (states[cols[k]].mode != PQWD_MODE_DICT) continue;
@@ -339,6 +476,12 @@ Status ParquetSink::encode_dict_columns(const DeviceBatch& b, const int* cols, i
       h.non_null = (int64_t)g.non_null;
       h.body = (const uint8_t*)host.get() + g.base;
       h.bytes = (size_t)body;
+      if (lz4()) {
+        const size_t i = (size_t)block_of[(size_t)(k * plan.base.n_pages + p)];
+        h.body = pk.block(i);
+        h.bytes = (size_t)pk.out[i].bytes;
+        h.uncompressed = (int64_t)body;
+      }
       h.encoding = ENCODING_RLE_DICTIONARY;
       held_[(size_t)cols[k]].push_back(h);
       const uint32_t levels = g.kind & ((1u << kPqwdRunShift) - 1u);
@@ -401,28 +544,45 @@ Status ParquetSink::open_group() {
 Status ParquetSink::close_group() {
   hipStream_t s = ctx().stream;
   std::vector<std::shared_ptr<void>> bodies(dict_.size());
+  std::vector<int64_t> block_of(dict_.size(), -1);  // "compression": a dictionary body's entry in pk
+  std::vector<PqwLz4In> in;
   bool any = false;
   for (size_t c = 0; c < dict_.size(); ++c) {
     const DictColumn& dc = dict_[c];
-    if (dc.launches == 0 || dc.body_bytes == 0) continue;
+    if (dc.launches == 0) continue;
+    if (lz4()) {  // (a dictionary without an entry is a block as well: a token of no literals)
+      block_of[c] = (int64_t)in.size();
+      in.push_back(PqwLz4In{(const uint8_t*)dc.body.get(), 0, (uint32_t)dc.body_bytes, 0});
+      continue;
+    }
+    if (dc.body_bytes == 0) continue;
     Status st;
     bodies[c] = pinned_alloc((size_t)dc.body_bytes, &st);
     if (!bodies[c]) return st;
     DFX_HIP(hipMemcpyAsync(bodies[c].get(), dc.body.get(), (size_t)dc.body_bytes, hipMemcpyDeviceToHost, s));
     any = true;
   }
+  PackedBodies pk;
+  if (!in.empty()) {  // one launch per group for its dictionary bodies
+    DFX_RETURN_IF_ERROR(pack_bodies(std::move(in), &pk));
+    any = true;
+  }
   if (any) DFX_HIP(hipStreamSynchronize(s));  // the dictionary bodies: once per row group
+  if (pk.out) DFX_RETURN_IF_ERROR(check_packed(pk));
   writer_.begin_row_group();
   for (size_t c = 0; c < held_.size(); ++c) {
     writer_.begin_chunk(c);
     if (dict_[c].launches > 0) {
-      if (!writer_.add_dictionary_page((int64_t)dict_[c].entries, bodies[c].get(), (size_t)dict_[c].body_bytes)) return io_error();
+      const bool packed = block_of[c] >= 0;
+      if (!(packed ? writer_.add_dictionary_page((int64_t)dict_[c].entries, pk.block((size_t)block_of[c]), (size_t)pk.out[block_of[c]].bytes, (int64_t)dict_[c].body_bytes)
+                   : writer_.add_dictionary_page((int64_t)dict_[c].entries, bodies[c].get(), (size_t)dict_[c].body_bytes)))
+        return io_error();
       ++counters().parquet_write_dict_pages;
       counters().parquet_write_dict_entries += (long long)dict_[c].entries;
       dict_[c].launches = 0;
     }
     for (const HeldPage& h : held_[c])
-      if (!writer_.add_page(h.num_values, h.non_null, h.body, h.bytes, h.encoding)) return io_error();
+      if (!writer_.add_page(h.num_values, h.non_null, h.body, h.bytes, h.encoding, h.uncompressed)) return io_error();
     held_[c].clear();
   }
   writer_.end_row_group(group_rows_);

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "dfx_parquet_dict_enc.hpp"
+#include "dfx_parquet_lz4_enc.hpp"
 
 namespace dfx {
 
@@ -96,5 +97,25 @@ static_assert(sizeof(DevPqwdPlan) <= 4096, "the plan is a kernel argument");
 hipError_t launch_pqwd_measure(const DevPqwdPlan& plan, uint32_t* slot_of_row, PqwdTile* tiles, pqw::PqwPage* pages, hipStream_t s);
 hipError_t launch_pqwd_encode(const DevPqwdPlan& plan, const uint32_t* slot_of_row, const PqwdTile* tiles, const pqw::PqwPage* pages, uint8_t* out,
                               uint64_t out_bytes, uint64_t* ctrl, hipStream_t s);
+
+// ---- the "compression" option (dfx_k_parquet_write_lz4.hip; the block rule: dfx_parquet_lz4_enc.hpp) ---------------------------------
+// After a chain's encode kernel the host, which has read the chain's page table back, names every body of the launch to k_pqw_lz4 (a
+// wave per page: the body as one raw LZ4 block in a slot of its own) -> k_pqw_lz4_bases (the sizes into 8-byte-aligned bases) ->
+// [host reads the sizes and bases back, sizes the packed buffer] -> k_pqw_lz4_compact (every block to its base).
+struct PqwLz4In {      // per page, built by the host
+  const uint8_t* src;  // the body on the device
+  uint64_t slot_off;   // of its slot of lz4_bound(len) bytes in the slot buffer, 8-byte aligned
+  uint32_t len;        // bytes of the body
+  uint32_t pad;
+};
+struct PqwLz4Out {     // per page, read back; entry [pages] holds the packed buffer's length in `base`
+  uint64_t base;       // of the block in the packed buffer, 8-byte aligned (k_pqw_lz4_bases)
+  uint32_t bytes;      // of the block
+  uint32_t sequences;
+};
+// ctrl: bit 1 set when a sequence would leave its slot, or a slot or a base lies outside its buffer (that wave stores nothing more)
+hipError_t launch_pqw_lz4(const PqwLz4In* in, int64_t n_pages, uint8_t* slots, uint64_t slots_bytes, PqwLz4Out* out, uint64_t* ctrl, hipStream_t s);  // out: n_pages + 1
+hipError_t launch_pqw_lz4_compact(const PqwLz4In* in, const PqwLz4Out* out, int64_t n_pages, const uint8_t* slots, uint64_t slots_bytes, uint8_t* packed,
+                                  uint64_t packed_bytes, uint64_t* ctrl, hipStream_t s);
 
 }  // namespace dfx

@@ -328,11 +328,18 @@ def write_csv(relation: Relation, filename: str, options: Optional[dict] = None)
     return rows.value, nbytes.value
 
 
+# values of write_parquet's "compression" option: Parquet codec ids
+PARQUET_COMPRESSION_UNCOMPRESSED = 0
+PARQUET_COMPRESSION_LZ4_RAW = 7
+
+
 def write_parquet(relation: Relation, filename: str, options: Optional[dict] = None):
     """The executor of PhysicalPlan::Write { plan, filename, kind: Parquet } (physicalplan.rs:24-29; the reference has none):
-    consumes `relation` to its end and writes it to `filename` as an uncompressed Parquet file of PLAIN V1 pages encoded on the
-    device (include/dfx.h: dfx_parquet_write has the format).  Returns (rows, bytes of the file).  `options`: "row_group_rows"
-    (default 2^20, >= 1) and "page_rows" (default 2^15, a multiple of 64); any other key is refused."""
+    consumes `relation` to its end and writes it to `filename` as a Parquet file of V1 pages encoded on the device (include/dfx.h:
+    dfx_parquet_write has the format).  Returns (rows, bytes of the file).  `options`: "row_group_rows" (default 2^20, >= 1),
+    "page_rows" (default 2^15, a multiple of 64), "dictionary" (default 0: PLAIN pages only; N: dictionary-encoded chunks of at most
+    N entries) and "compression" (default PARQUET_COMPRESSION_UNCOMPRESSED; PARQUET_COMPRESSION_LZ4_RAW: every page body one raw
+    LZ4 block, packed on the device); any other key is refused."""
     err = _errbuf()
     opts, n_opts, _keep = _options(options)
     rows, nbytes = ctypes.c_int64(), ctypes.c_int64()

@@ -421,15 +421,25 @@ int32_t dfx_csv_write(struct ArrowArrayStream* input, const char* filename, cons
  *             dictionary beyond N entries, or its body to 2^31 - 1 bytes, turns the chunk PLAIN from that launch to its end (the
  *             dictionary pages already held stay; a chunk that falls back in its first launch is byte for byte the chunk written
  *             without the option).  A new row group starts every column with an empty dictionary.  Boolean columns stay PLAIN
+ *   compression  "compression" = 7 (LZ4_RAW): every column chunk carries codec 7 and every page body -- data pages stay V1, so the
+ *             level block and the values together; under "dictionary" the dictionary page and the index pages as well -- is ONE raw
+ *             LZ4 block (no frame, no length prefix), packed on the device by the rule of csrc/dfx_parquet_lz4_enc.hpp, which is
+ *             deterministic: a file is byte for byte what the sequential host encoder of that header writes.  V1 has no "stored"
+ *             form: a page that does not shrink is still a valid block (the reader accepts it: its header pass counts such pages as oversized_v1_pages); an
+ *             empty body (the dictionary of an all-null chunk) is the one-byte block {0x00}.  PageHeader carries both sizes;
+ *             ColumnMetaData's total_uncompressed_size and total_compressed_size both include the page headers
  * `options`: "row_group_rows" (default 2^20, any value >= 1), "page_rows" (default 2^15; a multiple of 64, 64 .. 2^30), "dictionary"
  * (default 0: PLAIN pages only, files byte for byte what they are without the key; 1 .. 2^20: the most entries of a chunk's
  * dictionary), "dictionary_hash_bits" (debug; 1 .. 64, default 64: the device's hash of a Utf8 value is cut to that many bits, so
  * that a test can make two strings collide and see the chunk fall back to PLAIN; means nothing without "dictionary"); "dictionary" > 0
- * takes "page_rows" of at most 2^20 (the dictionary kernels keep a word per row and column of a launch); any other key
+ * takes "page_rows" of at most 2^20 (the dictionary kernels keep a word per row and column of a launch); "compression" (a Parquet
+ * codec id; default 0, UNCOMPRESSED: nothing new runs and files are byte for byte what they are without the key; 7: LZ4_RAW; any other
+ * value -- SNAPPY, GZIP, BROTLI, ZSTD, the deprecated LZ4 -- is refused: they are not written); any other key
  * or value is DFX_GENERAL naming the key, before a device is asked for.  Errors: a column type outside Boolean .. Utf8 is DFX_NOT_IMPLEMENTED naming the column and the type,
  * before a file exists and before a device is asked for; no device is DFX_EXECUTION_ERROR (there is no host encoding path); a path
  * that cannot be created or written is DFX_IO_ERROR; a REQUIRED field whose batch arrives with nulls is DFX_EXECUTION_ERROR naming
- * the column; a page body of 2^31 - 1 bytes or more is DFX_EXECUTION_ERROR (the page header's sizes are i32).  The bytes go to
+ * the column; a page body of 2^31 - 1 bytes or more is DFX_EXECUTION_ERROR (the page header's sizes are i32), and so is, under
+ * "compression" = 7, a body whose block's bound, n + n / 255 + 16, exceeds 2^31 - 1.  The bytes go to
  * `filename` + ".dfx-partial" and are renamed at the end: a failed call leaves nothing under either name.
  * ---------------------------------------------------------------------------------------- */
 int32_t dfx_parquet_write(struct ArrowArrayStream* input, const char* filename, const dfx_option* options, int32_t n_options,
@@ -618,7 +628,10 @@ int32_t dfx_set_option(const char* key, int64_t value);
  *                                 pages written / the entries they hold ("parquet_write_pages" keeps counting data pages only)
  *   "parquet_write_dict_index_pages", "parquet_write_dict_rle_index_pages"   data pages of dictionary indices / of them, pages whose
  *                                 indices are one RLE run (all equal)
- *   "parquet_write_dict_fallback_chunks"   chunks that left dictionary mode for PLAIN, a fallback in the first launch included */
+ *   "parquet_write_dict_fallback_chunks"   chunks that left dictionary mode for PLAIN, a fallback in the first launch included
+ *   "parquet_write_lz4_pages", "parquet_write_lz4_bytes_in", "parquet_write_lz4_bytes_out", "parquet_write_lz4_sequences"
+ *                                 "compression" = 7 (tests/test_gpu_parquet_lz4_write.py): page bodies packed into LZ4 blocks on the
+ *                                 device, dictionary pages included / their bytes / the blocks' bytes / the blocks' sequences */
 int64_t dfx_counter_get(const char* name);
 void dfx_counter_reset(void);
 

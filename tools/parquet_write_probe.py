@@ -11,7 +11,10 @@ library's own Parquet source takes to scan each of the two files.
 Single runs on a shared machine: no threshold is derived from them and no test times anything.
 With `--host-encoder EXE` (beside `--dictionary N`; needs no GPU) it writes the same three seeded tables with the sequential host encoder
 instead -- EXE is tests/native/parquet_dict_write_check.cpp built -- and prints the file sizes the device's files must have.
-usage: parquet_write_probe.py [rows, default 2^24] [out=<directory>, default /dev/shm or the temp directory] [--dictionary N [--host-encoder EXE]]"""
+With `--compression 7` it probes the "compression" option: the two tables written without the option and with it (beside
+`--dictionary N`: both with the dictionary) -- file bytes, the time of the `parquet_write` kernels and of the `parquet_write_lz4`
+kernels, the whole call, the option's counters, and the scan of each file by the library's own Parquet source.
+usage: parquet_write_probe.py [rows, default 2^24] [out=<directory>, default /dev/shm or the temp directory] [--dictionary N [--host-encoder EXE]] [--compression 7]"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,6 +25,11 @@ dictionary = 0
 if "--dictionary" in sys.argv:
     at = sys.argv.index("--dictionary")
     dictionary = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+compression = 0
+if "--compression" in sys.argv:
+    at = sys.argv.index("--compression")
+    compression = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
 host_encoder = None
 if "--host-encoder" in sys.argv:
@@ -110,8 +118,39 @@ def probe_dictionary():
         del t
 
 
+LZ4_COUNTERS = ["parquet_write_lz4_pages", "parquet_write_lz4_bytes_in", "parquet_write_lz4_bytes_out", "parquet_write_lz4_sequences"]
+
+
+def probe_compression():
+    base = {"dictionary": dictionary} if dictionary > 0 else {}
+    for what, nullable, distinct in DICT_TABLES[:2]:
+        schema, pieces = table(nullable, distinct)
+        t = ex.DeviceTable.from_batches(schema, pieces)
+        del pieces
+        print(f"parquet write compression probe ({what}): rows={rows}")
+        for options in (dict(base), dict(base, compression=compression)):
+            run = lambda: ex.write_parquet(t.scan(0), out, options)
+            wall = timed(run)
+            ex.profile_reset(); ex.profile_enable(True); ex.counter_reset()
+            _, nbytes = run()
+            ex.profile_enable(False)
+            prof = {p["kernel"]: p for p in ex.profile_snapshot()}
+            counters = {k: ex.counter_get(k) for k in COUNTERS + LZ4_COUNTERS}
+            def scan():
+                for _ in ex.ParquetDataSource(out): pass
+            scan_wall = timed(scan)
+            lz4_ms = prof["parquet_write_lz4"]["total_ms"] if "parquet_write_lz4" in prof else 0.0
+            print(f"  options {options or 'none'}: file={nbytes} bytes ({nbytes / rows:.1f} per row); kernels parquet_write {prof['parquet_write']['total_ms']:.3f} ms, "
+                  f"parquet_write_lz4 {lz4_ms:.3f} ms; whole call (mean of 3) {wall * 1e3:.1f} ms; scan of the file by the Parquet source (mean of 3) {scan_wall * 1e3:.1f} ms")
+            print(f"    counters: {counters}")
+        del t
+
+
 try:
     import pyarrow.compute  # noqa: F401
+    if compression > 0:
+        probe_compression()
+        sys.exit(0)
     if dictionary > 0:
         host_sizes() if host_encoder else probe_dictionary()
         sys.exit(0)
